@@ -12,7 +12,10 @@ resident in HBM before the timed region.  iar is a sequential Krylov recurrence 
 workload (weak scaling) and `value` is the whole-job rate: sum over ranks of converged eigenpairs
 divided by the max-over-ranks wall time.
 
-The JSON line also carries
+A plain run sets up, warms up, times the --steps steps and prints the headline fields of the JSON line (`metric`, `value`,
+`unit`, `ms_per_step`, `config`, the warm-up record); `--dump-outputs DIR` also writes what the last timed step returned
+(eigenvalues, eigenvectors) as DIR/<name>.npy.  With --full the run goes on to every other measurement and check, and the
+JSON line also carries
   value_excl_setup   the same rate with the linear-solver set-up (numeric LU + device-built block inverses)
                      taken out of every step (set-up time from the instrumented run)
   kernels / phase_share   per-phase time of one instrumented iar run and each phase's share of it
@@ -60,6 +63,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--n", type=int, default=9956)
     ap.add_argument("--maxit", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check besides the headline steps: host-LU and device-resident steps, parity of "
+                         "the returned pairs, instrumented phases, rooflines, fresh-process and 2-CPU calls, CPU baseline, C3, the sharded "
+                         "contour_beyn extra (C4) and C5; the --no-* options below apply to this mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (eigenvalues, eigenvectors) as DIR/<name>.npy, float64, complex values "
+                         "as a trailing (real, imag) axis")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-maxit", type=int, default=0, help="CPU oracle iterations (0 = the benchmark's own maxit)")
     ap.add_argument("--permc", default=None)
@@ -80,6 +90,26 @@ def parse():
                     help="run only one fixed-shape kernel loop (the command the committed rocprofv3 summaries come from)")
     ap.add_argument("--reps", type=int, default=50)
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 60 << 20     # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy in float64, a complex one with a trailing (real, imag) axis; an array that
+    would take the total over DUMP_LIMIT_BYTES keeps a fixed, seeded sample of its rows (in row order)"""
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if np.iscomplexobj(a):
+            a = np.stack([a.real, a.imag], axis=-1)
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > budget:
+            keep = budget // max(a.nbytes // max(a.shape[0], 1), 1)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        budget -= a.nbytes
 
 
 def event_loop(fn, reps, warm=5):
@@ -804,12 +834,15 @@ def main():
     dt = time.perf_counter() - t0
     native_steps = na.iar.native_runs - native0
     cpu_s_per_call = (cpu_seconds() - c0) / args.steps        # host CPU of this rank, all threads, per timed step
-    nres = max(2, min(5, args.steps))
-    torch.cuda.synchronize(); tr0 = time.perf_counter()
-    for _ in range(nres):
-        lam, Q = bc.c2_device(na, nep, args.maxit, args.permc)
-    torch.cuda.synchronize()
-    ms_resident = (time.perf_counter() - tr0) / nres * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"eigenvalues": lam, "eigenvectors": Qh_last})
+    if args.full:
+        nres = max(2, min(5, args.steps))
+        torch.cuda.synchronize(); tr0 = time.perf_counter()
+        for _ in range(nres):
+            lam, Q = bc.c2_device(na, nep, args.maxit, args.permc)
+        torch.cuda.synchronize()
+        ms_resident = (time.perf_counter() - tr0) / nres * 1e3
     if use_dist:
         t = torch.tensor([dt, float(pairs)], dtype=torch.float64, device=RED_DEV)
         tmax = t.clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -818,7 +851,7 @@ def main():
 
     # the same step with the numeric factorisation on the host (SuperLU) every time, for comparison
     ms_host_lu = None
-    if os.environ.get("NEP_LU_DEV", "1") != "0" and not args.only:
+    if args.full and os.environ.get("NEP_LU_DEV", "1") != "0" and not args.only:
         os.environ["NEP_LU_DEV"] = "0"
         try:
             bc.c2_device(na, nep, args.maxit, args.permc)
@@ -831,10 +864,38 @@ def main():
 
     out = None
     if rank == 0:
+        ms_step = dt / args.steps * 1e3
+        per_step_pairs = pairs / (args.steps * world)
+        out = {
+            "metric": "eigenpairs/sec (gun SPMF iar m=%d) + compute_Mlincomb GB/s" % args.maxit,
+            "value": pairs / dt, "unit": "eigenpairs/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f64 (complex128)", "data": "synthetic",
+            "config": {"workload": "nep_gallery gun SPMF (n=%d, 4 sparse terms, gun-like stand-in K,M + reference W1,W2), "
+                                   "shift_and_scale(250^2, 330^2-220^2), iar sigma=0 maxit=%d neigs=Inf tol=1e-10 "
+                                   "check_error_every=1 DGKS umfpack_refinements=10; numeric factorisation of M(sigma) "
+                                   "(UMFPACK-like symmetric strategy) inside the step" % (args.n, args.maxit),
+                       "parallelism": "replicas x%d (iar does not shard)" % world,
+                       "factorization": "numeric LU of M(sigma) inside every step: on the device (csrc/lufac.hip, right-looking on the "
+                                        "fill pattern and pivot sequence of the pattern's first host SuperLU factorisation, health "
+                                        "word + host fallback) when the plan of the pattern exists (built during warm-up), else host SuperLU",
+                       "eigenpairs_per_step": per_step_pairs},
+            "returns": "eigenvalues + eigenvectors on the host (download inside the timed step)",
+            "cpu_s_per_call": cpu_s_per_call,     # host CPU seconds per timed step (getrusage, all threads of this rank)
+            "eig_route": os.environ.get("NEP_IAR_EIG", "dev") + " (eig(H_k) of every step: csrc/hesseig.hip on the device | LAPACK on host threads)",
+            "driver": "the whole call after the factorisation is ONE C-ABI call, nep_iar_run (csrc/iar_run.hip): %d of the %d timed steps took it (the "
+                      "rest: the step-at-a-time Python pipeline); the same entry point the Julia method iar(::DeviceSPMF) calls"
+                      % (native_steps, args.steps),
+            "warmup_calls_ms": warm_ms,           # the first call carries every one-off: symbolic schedule, host LU, allocator pools
+            "settle_calls_ms": settle_ms,         # extra untimed calls after the device-LU plan became ready (when W < 4)
+            "plan_wait_ms": plan_wait_ms,         # time the warm-up still had to wait for the device-LU plan (background thread)
+        }
+    if rank == 0 and args.full:
         # independent parity check of the returned pairs (host FP64, reference residual criterion)
         Qh = Qh_last                     # the host block the last TIMED step returned
         errs = bc.host_backward_errors(nep.get_Av(), nep.get_fv(), lam, Qh)
         maxres = max(errs + [0.0])
+        out["config"]["max_backward_error"] = maxres
         # set-up share: median of 5 separately timed create_linsolver calls (host factorisation + device schedule; the
         # device-side block inverses run asynchronously behind it and are waited for here)
         ts = []
@@ -853,36 +914,11 @@ def main():
         byts, ms = mlincomb_roofline(na, nep, k)
         byts1, ms1 = mlincomb_roofline(na, nep, 1)
         achieved = byts / (ms * 1e-3) / 1e9
-        ms_step = dt / args.steps * 1e3
-        per_step_pairs = pairs / (args.steps * world)
-        out = {
-            "metric": "eigenpairs/sec (gun SPMF iar m=%d) + compute_Mlincomb GB/s" % args.maxit,
-            "value": pairs / dt, "unit": "eigenpairs/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f64 (complex128)", "data": "synthetic",
-            "config": {"workload": "nep_gallery gun SPMF (n=%d, 4 sparse terms, gun-like stand-in K,M + reference W1,W2), "
-                                   "shift_and_scale(250^2, 330^2-220^2), iar sigma=0 maxit=%d neigs=Inf tol=1e-10 "
-                                   "check_error_every=1 DGKS umfpack_refinements=10; numeric factorisation of M(sigma) "
-                                   "(UMFPACK-like symmetric strategy) inside the step" % (args.n, args.maxit),
-                       "parallelism": "replicas x%d (iar does not shard)" % world,
-                       "factorization": "numeric LU of M(sigma) inside every step: on the device (csrc/lufac.hip, right-looking on the "
-                                        "fill pattern and pivot sequence of the pattern's first host SuperLU factorisation, health "
-                                        "word + host fallback) when the plan of the pattern exists (built during warm-up), else host SuperLU",
-                       "eigenpairs_per_step": per_step_pairs,
-                       "max_backward_error": maxres},
-            "returns": "eigenvalues + eigenvectors on the host (download inside the timed step)",
+        out.update({
             "ms_per_step_device_resident": ms_resident,     # the same call leaving the eigenvector block in HBM (mean of a few calls after the timed region)
             "value_excl_setup": world * per_step_pairs / max(ms_step * 1e-3 - t_setup, 1e-9),
             "linsolver_setup_ms": t_setup * 1e3,
             "ms_per_step_host_lu": ms_host_lu,
-            "cpu_s_per_call": cpu_s_per_call,     # host CPU seconds per timed step (getrusage, all threads of this rank)
-            "eig_route": os.environ.get("NEP_IAR_EIG", "dev") + " (eig(H_k) of every step: csrc/hesseig.hip on the device | LAPACK on host threads)",
-            "driver": "the whole call after the factorisation is ONE C-ABI call, nep_iar_run (csrc/iar_run.hip): %d of the %d timed steps took it (the "
-                      "rest: the step-at-a-time Python pipeline); the same entry point the Julia method iar(::DeviceSPMF) calls"
-                      % (native_steps, args.steps),
-            "warmup_calls_ms": warm_ms,           # the first call carries every one-off: symbolic schedule, host LU, allocator pools
-            "settle_calls_ms": settle_ms,         # extra untimed calls after the device-LU plan became ready (when W < 4)
-            "plan_wait_ms": plan_wait_ms,         # time the warm-up still had to wait for the device-LU plan (background thread)
             "compute_Mlincomb_GBps": achieved,
             "roofline_compute_Mlincomb": {"bound": "hbm", "kernel": "nep_mlincomb, k=%d columns" % k,
                          "note": "the kernel BASELINE's metric names; at gun size one call moves 17.8 MB (2.2 us at 8 TB/s), "
@@ -893,7 +929,7 @@ def main():
                                            "achieved": byts1 / (ms1 * 1e-3) / 1e9}},
             "kernels": {"note": "wall ms per phase of one instrumented (step-synchronous) iar run",
                         **{k_: round(v * 1e3, 3) for k_, v in tm.items()}},
-        }
+        })
         dev_phases = ("linsolver_setup", "mlincomb", "solve", "orth", "ritz", "resid")
         tot = sum(tm.get(p, 0.0) for p in dev_phases)
         out["phase_share"] = {p: round(tm.get(p, 0.0) / tot, 3) for p in dev_phases} if tot > 0 else {}
@@ -966,7 +1002,7 @@ def main():
                 out["c3_nleigs"] = {"error": repr(e)[:300]}
     # extra (outside the headline timed region): the path that DOES shard -- Beyn's quadrature nodes over the ranks
     beyn = None
-    if not args.no_beyn:
+    if args.full and not args.no_beyn:
         # never lose the headline line because of the extra: an exception is recorded, and with several ranks a watchdog
         # covers the case of a rank stuck in the collective (the multi-rank RCCL exchange cannot be exercised on the 1-GPU
         # development box): after 120 s rank 0 prints the line without the extra and every rank leaves
@@ -988,7 +1024,7 @@ def main():
             beyn = {"error": repr(e)[:300]}
         if watchdog is not None:
             watchdog.cancel()
-    if rank == 0 and world == 1 and not args.no_c5:
+    if rank == 0 and world == 1 and args.full and not args.no_c5:
         try:
             out["c5_wep"] = c5_summary(na, args)
             try:
@@ -1002,7 +1038,8 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        out["beyn_sharded"] = beyn
+        if args.full:
+            out["beyn_sharded"] = beyn
         print(json.dumps(out))
     na.HostLUPool.shutdown()
 

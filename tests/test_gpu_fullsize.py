@@ -415,3 +415,35 @@ def test_c2_device_memory_plateaus(na):
         if i in (11, 35):
             marks.append(used())
     assert marks[1] - marks[0] < 48.0, marks
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(na, tmp_path):
+    """`bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR`, no --full: ONE JSON line with the headline fields and none of
+    the extras, `ms_per_step` = the time of one of the 3 timed steps, and in DIR the eigenpairs the last timed step returned (config
+    C2: 46 pairs, host FP64 backward errors below the tolerance)"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["unit"] == "eigenpairs/s" and d["higher_is_better"] is True and d["ms_per_step"] > 0
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - d["config"]["eigenpairs_per_step"]) < 1e-9 * d["value"]
+    # what really ran: the calls counted by nep_iar_run inside the timed loop, and the warm-up calls timed one by one
+    assert ": 3 of the 3 timed steps took it" in d["driver"], d["driver"]
+    assert len(d["warmup_calls_ms"]) == 1
+    assert not any(k in d for k in ("roofline", "cpu_baseline", "beyn_sharded", "c5_wep", "ms_per_step_host_lu"))
+    e = np.load(tmp_path / "eigenvalues.npy")
+    q = np.load(tmp_path / "eigenvectors.npy")
+    assert e.dtype == np.float64 and q.dtype == np.float64
+    lam = e[:, 0] + 1j * e[:, 1]
+    Q = q[..., 0] + 1j * q[..., 1]
+    nep = na.nep_gallery("gun_spmf_scaled")
+    assert len(lam) == d["config"]["eigenpairs_per_step"] == 46 and Q.shape == (nep.n, 46)
+    errs = _bc().host_backward_errors(nep.get_Av(), nep.get_fv(), lam, Q)
+    assert max(errs) < 1e-10

@@ -811,6 +811,48 @@ def test_bench_gpus_flag_and_launcher_must_agree():
     assert "args.gpus" in src and "torch.distributed.run" in src
 
 
+def test_bench_dump_outputs_writes_float64_and_samples_past_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: each returned array as <name>.npy in float64, complex values with a trailing (real, imag) axis; an
+    array that would take the total over the limit keeps a fixed, seeded sample of its rows, in row order, the same on every run.
+    The options are on the command line, the extras behind --full."""
+    import importlib.util
+    import subprocess
+    import sys
+    path = os.path.join(ROOT, "bench.py")
+    r = subprocess.run([sys.executable, path, "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    spec = importlib.util.spec_from_file_location("_bench", path)
+    bench = importlib.util.module_from_spec(spec)
+    # bench.py's module level sets thread-count defaults in os.environ and puts ROOT and scripts/ on sys.path: none of it may
+    # outlive this test
+    env0 = dict(os.environ)
+    monkeypatch.setattr(sys, "path", list(sys.path))
+    try:
+        spec.loader.exec_module(bench)
+    finally:
+        for k_ in set(os.environ) - set(env0):
+            del os.environ[k_]
+        os.environ.update(env0)
+    rng = np.random.default_rng(3)
+    lam = rng.standard_normal(7) + 1j * rng.standard_normal(7)
+    Q = np.ascontiguousarray((rng.standard_normal((50, 7)) + 1j * rng.standard_normal((50, 7))).T).T     # a transposed view, as iar returns it
+    bench.dump_outputs(str(tmp_path / "a"), {"eigenvalues": lam, "eigenvectors": Q})
+    e = np.load(tmp_path / "a" / "eigenvalues.npy")
+    v = np.load(tmp_path / "a" / "eigenvectors.npy")
+    assert e.dtype == np.float64 and e.shape == (7, 2) and np.array_equal(e[:, 0] + 1j * e[:, 1], lam)
+    assert v.dtype == np.float64 and v.shape == (50, 7, 2) and np.array_equal(v[..., 0] + 1j * v[..., 1], Q)
+    limit = e.nbytes + 20 * 7 * 16
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", limit)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"eigenvalues": lam, "eigenvectors": Q})
+    assert np.array_equal(np.load(tmp_path / "b" / "eigenvalues.npy"), e)
+    vb = np.load(tmp_path / "b" / "eigenvectors.npy")
+    assert vb.shape == (20, 7, 2) and np.array_equal(vb, np.load(tmp_path / "c" / "eigenvectors.npy"))
+    rows = [int(np.flatnonzero((Q == (x[:, 0] + 1j * x[:, 1])).all(axis=1))[0]) for x in vb]
+    assert rows == sorted(set(rows)) and len(rows) == 20
+    assert e.nbytes + vb.nbytes <= limit and bench.DUMP_LIMIT_BYTES <= 64e6
+
+
 # ---- a small model of Julia's Array / SubArray addressing, to evaluate the pointer expressions of julia/NEPMI355X.jl -------------
 class _JArray:
     """column-major Array{ComplexF64,N} at byte address `base`"""
