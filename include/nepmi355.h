@@ -323,6 +323,14 @@ int32_t nep_lu_refactor(nep_lu* lu, const nep_cdouble* hLx, const nep_cdouble* h
  * first kernel of the solve).  h_rs: n doubles, NULL removes it. */
 int32_t nep_lu_set_row_scale(nep_lu* lu, const double* h_rs);
 int32_t nep_lu_destroy(nep_lu* lu);
+/* X = A^{-T} B (conj = 0) or A^{-H} B (conj = 1) with the factors `lu` holds: the factor pair (U^T D^-1, D L^T), D = diag(U)
+ * (conjugated for conj = 1), perm_r and perm_c swapped.  A row scale rs of `lu` (Pr diag(rs) A Pc = LU) becomes an OUTPUT scale:
+ * x = rs .* y (the scale `lu` has at this call).  No factor value goes to the host and nothing is refactorised: the pair's values
+ * are gathered on the device from those of `lu`, its symbolic analysis runs once per pattern (cached).  `lu` is only read.
+ * The result is an ordinary handle (nep_lu_solve / _solve_add / _info / _schedule / _destroy; not nep_lu_refactor); either
+ * handle may be destroyed first.  NEP_ERR_UNSUPPORTED for a level-schedule handle (NEP_LU_SCHED=old, refused patterns).
+ * replaces: the second create_linsolver(..., nept, sigma) of src/method_infbilanczos.jl:62 and src/method_rfi.jl:63 */
+int32_t nep_lu_transpose(nep_lu* lu, int32_t conj, nep_lu** out);
 /* hint for the NEXT nep_lu_create of the calling thread: how many solves the factorisation will serve (default 50).
  * It sizes the dense tail block whose inverse is built at creation time (one-off ~T^2/256 us vs a shorter
  * dependency chain per solve): FactorizeLinSolver (iar/tiar: maxit solves) passes a large number,

@@ -121,6 +121,7 @@ SIGNATURES = {
     "nep_lu_create_csc": [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, P(c_vp)],
     "nep_lu_refactor": [c_vp, c_vp, c_vp],
     "nep_lu_set_row_scale": [c_vp, c_vp],
+    "nep_lu_transpose": [c_vp, c_i32, P(c_vp)],
     "nep_lu_is_block_schedule": [c_vp, P(c_i32)],
     "nep_lu_analyze": [c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, P(c_i64)],
     "nep_lu_destroy": [c_vp],

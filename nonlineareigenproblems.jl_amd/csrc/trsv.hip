@@ -89,6 +89,7 @@ struct nep_lu {
     int32_t csc = 0;               // layout the caller's factors came in (nep_lu_refactor expects the same)
     hipStream_t last = nullptr;    // stream of the last solve: frees are ordered behind it
     bool used = false;
+    bool transposed = false;       // made by nep_lu_transpose (its factors have no caller-side value layout to refactor)
 };
 
 __device__ __forceinline__ cplx cdiv(cplx a, cplx b) {
@@ -1013,7 +1014,23 @@ extern "C" {
 int32_t nep_lu_refactor(nep_lu* lu, const nep_cdouble* hLx, const nep_cdouble* hUx) {
     ARGCHK(lu && hLx && hUx);
     if (!lu->ml) { nep_set_error("nep_lu_refactor needs the block schedule (this handle uses the level schedule)"); return NEP_ERR_UNSUPPORTED; }
+    if (lu->transposed) { nep_set_error("nep_lu_refactor: a handle made by nep_lu_transpose has no input value layout"); return NEP_ERR_UNSUPPORTED; }
     return ml_refactor(lu->ml, hLx, hUx);
+}
+
+int32_t nep_lu_transpose(nep_lu* lu, int32_t conj, nep_lu** out) {
+    ARGCHK(lu && out && (conj == 0 || conj == 1));
+    *out = nullptr;
+    if (!lu->ml) { nep_set_error("nep_lu_transpose needs the block schedule (this handle uses the level schedule)"); return NEP_ERR_UNSUPPORTED; }
+    MLFactor* F = nullptr;
+    int rc = ml_transpose(lu->ml, conj, g_expected_solves, &F);
+    if (rc) return rc;
+    int64_t info[6];
+    ml_info(F, info, nullptr);
+    nep_lu* t = nep_lu_wrap_ml(F, lu->n, info[1], info[2]);
+    t->csc = 0; t->transposed = true;
+    *out = t;
+    return NEP_OK;
 }
 
 int32_t nep_lu_set_row_scale(nep_lu* lu, const double* h_rs) {

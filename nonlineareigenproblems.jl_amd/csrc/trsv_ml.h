@@ -34,3 +34,6 @@ int ml_create_from_sym(MLSym* S, const nep_cdouble* d_Lx, const nep_cdouble* d_U
 int ml_create_from_sym_batch(MLSym* S, int B, const nep_cdouble* const* d_Lx, const nep_cdouble* const* d_Ux, hipStream_t producer,
                              int expected_solves, MLFactor** out);
 int ml_wait_ready(MLFactor* F, hipStream_t st);   // st waits for the numeric build of F
+// factors of A^T (conj = 0) or A^H (conj = 1) from those of A: (U^T D^-1, D L^T), perm_r / perm_c swapped, a row scale of F
+// becomes an output scale.  Symbolic once per pattern (kept with F's), values gathered on the device from F's; F is only read.
+int ml_transpose(MLFactor* F, int conj, int expected_solves, MLFactor** out);

@@ -82,6 +82,13 @@ struct MLSym {
     // ... and its 9 T^2 workspace (253 MB on gun), kept with the pattern: one build at a time uses it, ordered by an event (a block
     // taken from the pool per factorisation and freed behind its stream made the pool's footprint depend on the timing of the calls)
     cplx* d_apex_work = nullptr; int64_t apex_work_T = 0; hipEvent_t apex_work_ev = nullptr; bool apex_work_used = false;
+    // the input patterns (layout `csc`) and permutations, kept for the symbolic analysis of the transposed factors (ml_transpose)
+    std::vector<int32_t> h_Lp, h_Li, h_Up, h_Ui, h_pr, h_pc;
+    bool has_pat = false;
+    // transposed pair (U^T D^-1, D L^T), built on the first ml_transpose: its symbolic (a referenced cache entry) and, per input
+    // entry of that pair (L' entries first), the d_vals position of the source value and of the diagonal it is scaled by (-1: none)
+    MLSym* tsym = nullptr;
+    int64_t* d_tsrc = nullptr; int64_t* d_tscl = nullptr; int64_t tnnzL = 0, tnnzU = 0;
 };
 
 struct MLFactor {
@@ -96,6 +103,7 @@ struct MLFactor {
     hipEvent_t apex_ev = nullptr; bool apex_live = false;
     int solves_since_numeric = 0;      // the switch to the apex happens at a FIXED solve of a factor (NEP_ML_APEX_AT), not when a query says so
     double* d_rscale = nullptr;    // optional row scaling (UMFPACK's Rs): b is multiplied by it on the way in
+    double* d_oscale = nullptr;    // output scaling (transposed factors of a row-scaled matrix): x = oscale .* y
     NepScratch work;               // bw | y | x | tmp, each n*nrhs
     hipEvent_t ready = nullptr;    // numeric build complete (recorded on the build stream)
     hipStream_t synced = nullptr;  // stream that has already waited for `ready`
@@ -827,6 +835,9 @@ void free_sym(MLSym* s) {
     if (s->d_apex_kr) nep_pool_free(s->d_apex_kr);
     if (s->apex_work_ev) { (void)hipEventSynchronize(s->apex_work_ev); (void)hipEventDestroy(s->apex_work_ev); }
     if (s->d_apex_work) nep_pool_free(s->d_apex_work);
+    if (s->d_tsrc) nep_pool_free(s->d_tsrc);
+    if (s->d_tscl) nep_pool_free(s->d_tscl);
+    if (s->tsym && s->tsym != s) s->tsym->refs--;   // callers hold g_cache_mu; the idle entry leaves the cache by the LRU rule
     delete s;
 }
 
@@ -1241,12 +1252,10 @@ static void sym_release(MLSym* s) {
     }
 }
 
-int ml_create(int64_t n, int csc, const int32_t* Lp, const int32_t* Li, const nep_cdouble* Lx, const int32_t* Up,
-              const int32_t* Ui, const nep_cdouble* Ux, const int32_t* perm_r, const int32_t* perm_c, int expected_solves,
-              MLFactor** out) {
+// the symbolic of a pair of factor patterns: a cache hit or a fresh build (cached).  Returns a referenced entry.
+static int sym_get(int64_t n, int csc, const int32_t* Lp, const int32_t* Li, const int32_t* Up, const int32_t* Ui,
+                   const int32_t* perm_r, const int32_t* perm_c, MLSym** out, bool* hit_out) {
     *out = nullptr;
-    const bool timing = getenv("NEP_TIMING") != nullptr;
-    const double t0 = ml_now_ms();
     uint64_t h0 = 0x243F6A8885A308D3ull ^ (uint64_t)n, h1 = 0x13198A2E03707344ull + (uint64_t)csc;
     hash_words(h0, h1, Lp, (size_t)(n + 1) * 4); hash_words(h0, h1, Li, (size_t)Lp[n] * 4);
     hash_words(h0, h1, Up, (size_t)(n + 1) * 4); hash_words(h0, h1, Ui, (size_t)Up[n] * 4);
@@ -1260,45 +1269,63 @@ int ml_create(int64_t n, int csc, const int32_t* Lp, const int32_t* Li, const ne
     const double t1 = ml_now_ms();
     MLSym* S = nullptr;
     bool hit = false;
-    {
-        std::lock_guard<std::mutex> lk(g_cache_mu);      // held during the symbolic build: concurrent creators of one
-        const bool nocache = getenv("NEP_ML_NOCACHE") != nullptr;   // pattern (Beyn) wait instead of duplicating it
-        if (!nocache)
-            for (auto it = g_cache.begin(); it != g_cache.end(); ++it)
-                if ((*it)->key0 == h0 && (*it)->key1 == h1 && (*it)->n == n && (*it)->nnzL == Lp[n] && (*it)->nnzU == Up[n]) {
-                    S = *it; g_cache.erase(it); g_cache.push_front(S); hit = true; break;
-                }
-        if (!S) {
-            S = new MLSym();
-            S->key0 = h0; S->key1 = h1; S->nnzL = Lp[n]; S->nnzU = Up[n]; S->csc = csc;
-            int rc;
-            if (csc) {
-                std::vector<int32_t> Lrp, Lci, Lsrc, Urp, Uci, Usrc;
-                transpose_pattern(n, Lp, Li, Lrp, Lci, &Lsrc);
-                transpose_pattern(n, Up, Ui, Urp, Uci, &Usrc);
-                rc = build_symbolic(S, n, Lrp.data(), Lci.data(), Lsrc.data(), Urp.data(), Uci.data(), Usrc.data(), Up, Ui,
-                                    perm_r, perm_c);
-            } else {
-                std::vector<int32_t> UTp, UTi;
-                transpose_pattern(n, Up, Ui, UTp, UTi, nullptr);
-                rc = build_symbolic(S, n, Lp, Li, nullptr, Up, Ui, nullptr, UTp.data(), UTi.data(), perm_r, perm_c);
+    std::lock_guard<std::mutex> lk(g_cache_mu);      // held during the symbolic build: concurrent creators of one
+    const bool nocache = getenv("NEP_ML_NOCACHE") != nullptr;   // pattern (Beyn) wait instead of duplicating it
+    if (!nocache)
+        for (auto it = g_cache.begin(); it != g_cache.end(); ++it)
+            if ((*it)->key0 == h0 && (*it)->key1 == h1 && (*it)->n == n && (*it)->nnzL == Lp[n] && (*it)->nnzU == Up[n]) {
+                S = *it; g_cache.erase(it); g_cache.push_front(S); hit = true; break;
             }
-            if (rc) { free_sym(S); return rc; }
-            S->t_build_ms = ml_now_ms() - t1;
-            g_cache.push_front(S);
+    if (!S) {
+        S = new MLSym();
+        S->key0 = h0; S->key1 = h1; S->nnzL = Lp[n]; S->nnzU = Up[n]; S->csc = csc;
+        int rc;
+        if (csc) {
+            std::vector<int32_t> Lrp, Lci, Lsrc, Urp, Uci, Usrc;
+            transpose_pattern(n, Lp, Li, Lrp, Lci, &Lsrc);
+            transpose_pattern(n, Up, Ui, Urp, Uci, &Usrc);
+            rc = build_symbolic(S, n, Lrp.data(), Lci.data(), Lsrc.data(), Urp.data(), Uci.data(), Usrc.data(), Up, Ui,
+                                perm_r, perm_c);
+        } else {
+            std::vector<int32_t> UTp, UTi;
+            transpose_pattern(n, Up, Ui, UTp, UTi, nullptr);
+            rc = build_symbolic(S, n, Lp, Li, nullptr, Up, Ui, nullptr, UTp.data(), UTi.data(), perm_r, perm_c);
         }
-        S->refs++;
+        if (rc) { free_sym(S); return rc; }
+        S->h_Lp.assign(Lp, Lp + n + 1); S->h_Li.assign(Li, Li + Lp[n]);
+        S->h_Up.assign(Up, Up + n + 1); S->h_Ui.assign(Ui, Ui + Up[n]);
+        if (perm_r) S->h_pr.assign(perm_r, perm_r + n);
+        if (perm_c) S->h_pc.assign(perm_c, perm_c + n);
+        S->has_pat = true;
+        S->t_build_ms = ml_now_ms() - t1;
+        g_cache.push_front(S);
     }
+    S->refs++;
+    *out = S;
+    if (hit_out) *hit_out = hit;
+    return NEP_OK;
+}
+
+int ml_create(int64_t n, int csc, const int32_t* Lp, const int32_t* Li, const nep_cdouble* Lx, const int32_t* Up,
+              const int32_t* Ui, const nep_cdouble* Ux, const int32_t* perm_r, const int32_t* perm_c, int expected_solves,
+              MLFactor** out) {
+    *out = nullptr;
+    const bool timing = getenv("NEP_TIMING") != nullptr;
+    const double t1 = ml_now_ms();
+    MLSym* S = nullptr;
+    bool hit = false;
+    int rc = sym_get(n, csc, Lp, Li, Up, Ui, perm_r, perm_c, &S, &hit);
+    if (rc) return rc;
     const double t2 = ml_now_ms();
     MLFactor* F = new MLFactor();
     F->sym = S;
     F->use_graph = expected_solves >= 3 ? 1 : 0;
     F->apex_la = choose_apex(S, expected_solves);
-    int rc = ml_numeric(F, Lx, Ux);
+    rc = ml_numeric(F, Lx, Ux);
     if (rc) { ml_destroy(F); return rc; }
     if (timing) {
-        fprintf(stderr, "[ml_create] n=%lld levels=%d blocks=%d hash %.3f ms, symbolic %s %.3f ms, numeric (host) %.3f ms\n",
-                (long long)n, S->nlev, S->nblk, t1 - t0, hit ? "hit" : "built", t2 - t1, ml_now_ms() - t2);
+        fprintf(stderr, "[ml_create] n=%lld levels=%d blocks=%d symbolic %s %.3f ms, numeric (host) %.3f ms\n",
+                (long long)n, S->nlev, S->nblk, hit ? "hit" : "built", t2 - t1, ml_now_ms() - t2);
         if (!hit)
             for (int l = 0; l < S->nlev; ++l)
                 fprintf(stderr, "[ml_create]   level %d: rows %d blocks %d | L coupling %lld %s ch %d | U coupling %lld %s ch %d\n", l,
@@ -1517,6 +1544,144 @@ int ml_set_row_scale(MLFactor* F, const double* h_rs) {
     return NEP_OK;
 }
 
+// ---- transposed solves from the same factors ------------------------------------------------------------------------------
+// Pr A Pc = L U, D = diag(U)  =>  Pc^T A^T Pr^T = (U^T D^-1)(D L^T): a unit lower factor L' = U^T D^-1, an upper factor U' = D L^T and
+// the two permutations swapped.  The pair's values are gathered from the d_vals of the original factor (input layout of the pair:
+// CSR, L' strictly lower, U' with its diagonal first in every row), then the ordinary device-side numeric set-up runs on them.
+__global__ void k_ml_tgather(int64_t nL, int64_t ntot, const int64_t* __restrict__ src, const int64_t* __restrict__ scl,
+                             const cplx* __restrict__ vals, int conj, cplx* __restrict__ out) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < ntot; e += (int64_t)gridDim.x * blockDim.x) {
+        cplx a = vals[src[e]];
+        if (conj) a.y = -a.y;
+        const int64_t s = scl[e];
+        if (s >= 0) {
+            cplx d = vals[s];
+            if (conj) d.y = -d.y;
+            a = e < nL ? ml_cdiv(a, d) : cmul(a, d);     // L'(j,i) = U(i,j) / U(i,i);  U'(j,i) = U(j,j) L(i,j)
+        }
+        out[e] = a;
+    }
+}
+
+// X = scale * (oscale .* Y + Add): the output scaling of a transposed row-scaled factor (Y: n x nrhs, ld n)
+__global__ void k_ml_oscale(int64_t n, int nrhs, const cplx* __restrict__ Y, const double* __restrict__ osc, const cplx* add,
+                            int64_t ldadd, double scale, cplx* X, int64_t ldx) {
+    const int64_t tot = n * (int64_t)nrhs;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < tot; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = t / n, i = t - r * n;
+        const cplx y = Y[t];
+        double vr = osc[i] * y.x, vi = osc[i] * y.y;
+        if (add) { const cplx ad = add[r * ldadd + i]; vr += ad.x; vi += ad.y; }
+        X[r * ldx + i] = cmake(scale * vr, scale * vi);
+    }
+}
+
+static std::mutex g_tr_mu;        // one builder of a pattern's transposed symbolic at a time
+
+// the transposed pair's symbolic and gather tables of S (once per pattern; S->tsym set on success)
+static int ml_transpose_symbolic(MLSym* S) {
+    const int64_t n = S->n;
+    const int64_t oL = 0, oLb = oL + S->L.ncoup, oU = oLb + S->L.nin, oUb = oU + S->U.ncoup, oD = oUb + S->U.nin;
+    const int64_t ntot_old = oD + n;
+    // CSC of the original L and U with the input entry index of every entry
+    std::vector<int32_t> Lcp, Lri, Lsrc, Ucp, Uri, Usrc;
+    if (S->csc) {
+        Lcp = S->h_Lp; Lri = S->h_Li; Ucp = S->h_Up; Uri = S->h_Ui;
+        Lsrc.resize(Lri.size()); Usrc.resize(Uri.size());
+        for (size_t e = 0; e < Lsrc.size(); ++e) Lsrc[e] = (int32_t)e;
+        for (size_t e = 0; e < Usrc.size(); ++e) Usrc[e] = (int32_t)e;
+    } else {     // transpose_pattern turns a CSR pattern into the CSC one just as well
+        transpose_pattern(n, S->h_Lp.data(), S->h_Li.data(), Lcp, Lri, &Lsrc);
+        transpose_pattern(n, S->h_Up.data(), S->h_Ui.data(), Ucp, Uri, &Usrc);
+    }
+    std::vector<int32_t> newpos(n);
+    for (int64_t q = 0; q < n; ++q) newpos[S->h_oldof[q]] = (int32_t)q;
+    auto loc = [&](const MLFacSym& f, int64_t obase, int64_t obin, int32_t e) -> int64_t {
+        const int32_t v = f.map[e];
+        const int kind = v & 3;
+        if (kind == 1) return obase + (v >> 2);
+        if (kind == 2) return obin + (v >> 2);
+        if (kind == 3) return oD + (v >> 2);
+        return -1;
+    };
+    // L' (CSR): row j = column j of U above the diagonal;  U' (CSR): row j = diagonal, then column j of L below it
+    std::vector<int32_t> Tlp(n + 1, 0), Tli, Tup(n + 1, 0), Tui;
+    std::vector<int64_t> src, scl;
+    Tli.reserve(Uri.size()); Tui.reserve(Lri.size() + n);
+    src.reserve(Uri.size() + Lri.size() + n); scl.reserve(src.capacity());
+    for (int64_t j = 0; j < n; ++j) {
+        for (int32_t e = Ucp[j]; e < Ucp[j + 1]; ++e) {
+            const int32_t i = Uri[e];
+            if (i > j) { nep_set_error("transpose: U is not upper triangular"); return NEP_ERR_ARG; }
+            if (i == j) continue;
+            const int64_t a = loc(S->U, oU, oUb, Usrc[e]);
+            if (a < 0) { nep_set_error("transpose: an entry of U has no stored value"); return NEP_ERR_ARG; }
+            Tli.push_back(i); src.push_back(a); scl.push_back(oD + newpos[i]);
+        }
+        Tlp[j + 1] = (int32_t)Tli.size();
+    }
+    const int64_t tnL = (int64_t)src.size();
+    for (int64_t j = 0; j < n; ++j) {
+        Tui.push_back((int32_t)j); src.push_back(oD + newpos[j]); scl.push_back(-1);
+        for (int32_t e = Lcp[j]; e < Lcp[j + 1]; ++e) {
+            const int32_t i = Lri[e];
+            if (i < j) { nep_set_error("transpose: L is not lower triangular"); return NEP_ERR_ARG; }
+            if (i == j) continue;
+            const int64_t a = loc(S->L, oL, oLb, Lsrc[e]);
+            if (a < 0) { nep_set_error("transpose: an entry of L has no stored value"); return NEP_ERR_ARG; }
+            Tui.push_back(i); src.push_back(a); scl.push_back(oD + newpos[j]);
+        }
+        Tup[j + 1] = (int32_t)Tui.size();
+    }
+    for (size_t e = 0; e < src.size(); ++e)       // every gather address inside the original value block
+        if (src[e] < 0 || src[e] >= ntot_old || scl[e] >= ntot_old) { nep_set_error("transpose: internal gather index"); return NEP_ERR_ARG; }
+    MLSym* T = nullptr;
+    int rc = sym_get(n, 0, Tlp.data(), Tli.data(), Tup.data(), Tui.data(), S->h_pc.empty() ? nullptr : S->h_pc.data(),
+                     S->h_pr.empty() ? nullptr : S->h_pr.data(), &T, nullptr);
+    if (rc) return rc;
+    if ((rc = up(&S->d_tsrc, src)) || (rc = up(&S->d_tscl, scl))) { sym_release(T); return rc; }
+    S->tnnzL = tnL; S->tnnzU = (int64_t)src.size() - tnL;
+    if (T == S) { std::lock_guard<std::mutex> lk(g_cache_mu); T->refs--; }   // the pair is its own transpose: no self reference
+    S->tsym = T;
+    return NEP_OK;
+}
+
+int ml_transpose(MLFactor* F, int conj, int expected_solves, MLFactor** out) {
+    *out = nullptr;
+    MLSym* S = F->sym;
+    if (!S->has_pat) { nep_set_error("transpose: the factor's patterns were not kept"); return NEP_ERR_UNSUPPORTED; }
+    int rc;
+    {
+        std::lock_guard<std::mutex> lk(g_tr_mu);
+        if (!S->tsym && (rc = ml_transpose_symbolic(S))) return rc;
+    }
+    MLSym* T = S->tsym;
+    const int64_t ntot = S->tnnzL + S->tnnzU;
+    cplx* d_T = nullptr;
+    if ((rc = nep_pool_alloc((void**)&d_T, (size_t)std::max<int64_t>(ntot, 1) * sizeof(cplx)))) return rc;
+    hipStream_t bst = g_bstreams.get();
+    HIPCHK(hipStreamWaitEvent(bst, F->ready, 0));            // the original's values are complete (read only from here on)
+    const int g = (int)std::min<int64_t>((ntot + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_ml_tgather, dim3(std::max(g, 1)), dim3(256), 0, bst, S->tnnzL, ntot, (const int64_t*)S->d_tsrc,
+                       (const int64_t*)S->d_tscl, (const cplx*)F->d_vals, conj, d_T);
+    LAUNCHCHK();
+    MLFactor* G = nullptr;
+    rc = ml_create_from_sym(T, (const nep_cdouble*)d_T, (const nep_cdouble*)(d_T + S->tnnzL), bst, expected_solves, &G);
+    if (rc == NEP_OK && F->d_rscale) {
+        if ((rc = nep_pool_alloc((void**)&G->d_oscale, (size_t)S->n * sizeof(double))) == NEP_OK &&
+            hipMemcpyAsync(G->d_oscale, F->d_rscale, (size_t)S->n * sizeof(double), hipMemcpyDeviceToDevice, bst) != hipSuccess)
+            rc = NEP_ERR_HIP;
+    }
+    // the pair's values have been gathered into G once its numeric set-up is ready: then d_T goes back to the pool, and neither
+    // handle depends on the other any more (either may be destroyed first)
+    if (rc == NEP_OK && hipEventSynchronize(G->ready) != hipSuccess) rc = NEP_ERR_HIP;
+    if (rc == NEP_OK && hipStreamSynchronize(bst) != hipSuccess) rc = NEP_ERR_HIP;
+    if (rc != NEP_OK) { (void)hipStreamSynchronize(bst); nep_pool_free(d_T); if (G) ml_destroy(G); return rc; }
+    nep_pool_free(d_T);
+    *out = G;
+    return NEP_OK;
+}
+
 void ml_destroy(MLFactor* F) {
     if (!F) return;
     // the solves enqueued on F->last may still read these blocks: the pool hands them out again only behind that work
@@ -1525,6 +1690,7 @@ void ml_destroy(MLFactor* F) {
     if (F->apex_ev) { (void)hipEventSynchronize(F->apex_ev); (void)hipEventDestroy(F->apex_ev); }
     nep_pool_free_on(F->d_vals, st, F->used); nep_pool_free_on(F->d_ixL, st, F->used); nep_pool_free_on(F->d_ixU, st, F->used);
     nep_pool_free_on(F->d_rscale, st, F->used); nep_pool_free_on(F->d_Sinv, st, F->used);
+    if (F->d_oscale) nep_pool_free_on(F->d_oscale, st, F->used);
     if (F->work.dptr) { nep_pool_free_on(F->work.dptr, st, F->used); F->work.dptr = nullptr; F->work.cap = 0; }
     if (F->graph) (void)hipGraphExecDestroy(F->graph);
     if (F->cap_stream) (void)hipStreamDestroy(F->cap_stream);
@@ -2065,6 +2231,10 @@ int ml_solve(MLFactor* F, int nrhs, const nep_cdouble* dB, int64_t ldb, const ne
     c.F = F; c.nrhs = nrhs; c.ld = n;
     c.bw = (cplx*)F->work.dptr; c.y = c.bw + (size_t)n * nrhs; c.x = c.y + (size_t)n * nrhs; c.tmp = c.x + (size_t)n * nrhs;
     c.dB = (const cplx*)dB; c.ldb = ldb; c.dX = (cplx*)dX; c.ldx = ldx; c.dAdd = (const cplx*)dAdd; c.ldadd = ldadd; c.scale = scale;
+    // output scaling (transposed factors of a row-scaled matrix): the last level writes the plain solution into bw (no longer read
+    // by then), one more launch forms X = scale * (oscale .* y + Add)
+    const bool osc = F->d_oscale != nullptr;
+    if (osc) { c.dX = c.bw; c.ldx = n; c.dAdd = nullptr; c.ldadd = 0; c.scale = 1.0; }
     int launches = 0;
     if (F->h_ferr && *F->h_ferr) {
         nep_set_error("block-schedule solve: a phase wait of the single-launch kernel hit its bound (earlier solve incomplete)");
@@ -2076,7 +2246,7 @@ int ml_solve(MLFactor* F, int nrhs, const nep_cdouble* dB, int64_t ldb, const ne
     // same-address increments per solve serialise at ~150 ns each, and the release/acquire fences are the same L2
     // write-back/invalidate a kernel boundary performs.  A kernel boundary (~2.5 us on this part) IS the cheap grid barrier.
     const char* fuse_env = nrhs == 1 ? getenv("NEP_ML_FUSE") : nullptr;
-    if (nrhs == 1 && !F->fuse_off && fuse_env && atoi(fuse_env)) {
+    if (nrhs == 1 && !F->fuse_off && !osc && fuse_env && atoi(fuse_env)) {
         // record the launches of the multi-launch path as phases and issue them as one kernel
         MLRecorder rec; rec.a.nph = 0; rec.a.total = 0; rec.overflow = false;
         g_rec = &rec;
@@ -2127,6 +2297,12 @@ int ml_solve(MLFactor* F, int nrhs, const nep_cdouble* dB, int64_t ldb, const ne
     if (!graphed && (rc = ml_middle(c, st, &launches))) return rc;
     if (u0_fused(F, nrhs)) { if ((rc = run_U0_fused(c, st, &launches))) return rc; }
     else if ((rc = run_U_level(c, 0, true, st, &launches))) return rc;
+    if (osc) {
+        const int g = (int)std::min<int64_t>((n * nrhs + 255) / 256, 4096);
+        hipLaunchKernelGGL(k_ml_oscale, dim3(g), dim3(256), 0, st, n, nrhs, (const cplx*)c.bw, (const double*)F->d_oscale,
+                           (const cplx*)dAdd, ldadd, scale, (cplx*)dX, ldx);
+        LAUNCHCHK(); ++launches;
+    }
     F->launches = launches;
     F->last = st; F->used = true;
     return NEP_OK;

@@ -436,6 +436,16 @@ class DeviceLU:
         rs = None if rs is None else np.ascontiguousarray(rs, dtype=np.float64)
         check(lib.nep_lu_set_row_scale(self.h, hptr(rs) if rs is not None else None))
 
+    def transpose(self, conj=False):
+        """factors of A^T (conj=False) or A^H (conj=True) from this handle's, without a host round trip or a refactorisation
+        (nep_lu_transpose); this handle is left as it was.  NepError (NEP_ERR_UNSUPPORTED) for a level-schedule handle."""
+        h = c_vp()
+        check(lib.nep_lu_transpose(self.h, 1 if conj else 0, C.byref(h)))
+        t = DeviceLU._from_handle(h, self.n, self.normA, dict(getattr(self, "strategy", None) or {}, transposed="H" if conj else "T"),
+                                  getattr(self, "growth", None))
+        t.device_factorized = getattr(self, "device_factorized", False)
+        return t
+
     def launches_last_solve(self):
         sch = (c_i64 * 8)()
         check(lib.nep_lu_schedule(self.h, sch))
