@@ -133,6 +133,19 @@ int32_t nep_mlincomb(nep_spmf* s, int32_t k, const nep_cdouble* hC, const nep_cd
 int32_t nep_mlincomb_dev(nep_spmf* s, int32_t k, const nep_cdouble* dC, int64_t ldc, const nep_cdouble* dV,
                          int64_t ldv, nep_cdouble* dz, nep_stream stream);
 
+/* K11  c = - sum_t sum_{j<ma} sum_{i<mb} tau[i+j+1 + t*ldt] * w_j^H A_t b_i: the left-right scalar product of the infinite
+ * bi-Lanczos method, the entrywise product of W^H A_t B with a Hankel matrix of Taylor coefficients.
+ * replaces: left_right_scalar_prod src/method_infbilanczos.jl:229-246 (ma calls of compute_Mlincomb on B scaled by
+ *           1/(j+i-1)!, each followed by dot(At[:,j], .)), called at :106, :151, :171.
+ * dW: n x ma (ldw), dB: n x mb (ldb), column-major device blocks.  dTau: device (ma+mb) x mt column-major (ldt >= ma+mb),
+ * tau[d + t*ldt] = f_t^(d)(sigma) / d! -- the layout of nep_mlincomb_dev's coefficient block (dTau + 1 with ldc = ldt gives
+ * sum_i M^(i)(sigma)/i! v_i).  Two launches, fixed reduction order (two calls give the same bits), A_t B is never stored.
+ * h_c != NULL: c to the host (synchronous); otherwise c to the device word d_c (asynchronous).
+ * NEP_ERR_UNSUPPORTED when ma or mb exceeds 256. */
+int32_t nep_lr_hankel(nep_spmf* s, int32_t ma, int32_t mb, const nep_cdouble* dW, int64_t ldw, const nep_cdouble* dB,
+                      int64_t ldb, const nep_cdouble* dTau, int64_t ldt, nep_cdouble* h_c, nep_cdouble* d_c,
+                      nep_stream stream);
+
 /* K2  residual batch: r_s = sum_i F[i,s] A_i q_s, s=1..k; returns ||r_s||_2 and ||q_s||_2.
  * replaces: k calls of estimate_error -> compute_Mlincomb(nep,lambda_s,q_s)
  *           src/errmeasure.jl:128-130,186-190; call sites src/method_iar.jl:134-135,

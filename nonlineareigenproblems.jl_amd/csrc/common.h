@@ -222,3 +222,15 @@ struct NepScratch {
     // The owner must not exit with kernels on the block still pending (iar's checker drains its stream before it returns).
     ~NepScratch() { release(); }
 };
+
+// spmv.hip: the stacked CSR of an SPMF handle (entries sorted by (col, term) per row) and a scratch block of its own, for
+// kernels in other files (lrprod.hip)
+struct NepSpmfView {
+    int64_t n;
+    int32_t mt, valbytes;
+    const int32_t* rowptr;
+    const uint32_t* idx;
+    const void* vals;
+    NepScratch* scratch;
+};
+extern "C" int nep_spmf_csr_view(nep_spmf* s, NepSpmfView* v);

@@ -31,6 +31,7 @@ struct nep_spmf {
     NepScratch part;          // per-block partials
     NepScratch cwpart;        // nep_cw_backward_error's own scratch: it runs on the solve stream while a residual batch
                               // (coef, part) may be in flight on another stream (iar's convergence checks)
+    NepScratch lrpart;        // nep_lr_hankel's per-workgroup partials (lrprod.hip)
     PinnedRing ring;          // pinned staging of host coefficient blocks
     PinnedRing cwring;        // ... of nep_cw_backward_error (may be called from another host thread than the residual batches)
 };
@@ -1014,9 +1015,18 @@ int32_t nep_spmf_destroy(nep_spmf* s) {
     s->coef.release();
     s->part.release();
     s->cwpart.release();
+    s->lrpart.release();
     s->ring.release();
     s->cwring.release();
     delete s;
+    return NEP_OK;
+}
+
+int nep_spmf_csr_view(nep_spmf* s, NepSpmfView* v) {
+    ARGCHK(s && v);
+    v->n = s->n; v->mt = s->mt; v->valbytes = s->valbytes;
+    v->rowptr = s->d_rowptr; v->idx = s->d_idx; v->vals = s->d_vals;
+    v->scratch = &s->lrpart;
     return NEP_OK;
 }
 

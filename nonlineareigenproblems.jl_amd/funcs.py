@@ -27,6 +27,16 @@ class ScalarFun:
         for gun, scale^j = 60500^j overflows at j = 65 while scale^j f^(j) stays below 1e165."""
         raise NotImplementedError
 
+    def taylor(self, lam, k, scale=1.0):
+        """array [scale^j f^(j)(lam) / j!, j = 0..k-1] (complex128): the Taylor coefficients of h -> f(lam + scale*h).  The
+        closed-form classes below run recurrences that never form f^(j) or j! on their own -- derivs of gun overflows near
+        order 170, where f^(j) grows like j!; the Taylor coefficients stay bounded.  Generic fallback: derivs, with the
+        factorial divided in step by step."""
+        d = np.array(self.derivs(lam, k, scale), dtype=np.complex128)
+        for j in range(2, k):
+            d[j:] /= j
+        return d
+
     def matfun(self, S):
         """f(S) for a square matrix S (host, small)."""
         raise NotImplementedError
@@ -69,6 +79,13 @@ class Monomial(ScalarFun):
             out[j] = (math.factorial(self.p) // math.factorial(self.p - j)) * lam ** (self.p - j) * scale ** j
         return out
 
+    def taylor(self, lam, k, scale=1.0):
+        lam = complex(lam)
+        out = np.zeros(k, dtype=np.complex128)
+        for j in range(min(k, self.p + 1)):
+            out[j] = math.comb(self.p, j) * lam ** (self.p - j) * scale ** j
+        return out
+
     def matfun(self, S):
         return np.linalg.matrix_power(np.asarray(S, dtype=complex), self.p)
 
@@ -87,6 +104,16 @@ class Exp(ScalarFun):
 
     def derivs(self, lam, k, scale=1.0):
         return np.exp(self.c * complex(lam)) * np.power(complex(self.c * scale), np.arange(k))
+
+    def taylor(self, lam, k, scale=1.0):
+        # tau_{j+1} = tau_j * (c scale) / (j+1)
+        out = np.empty(k, dtype=np.complex128)
+        d = complex(np.exp(self.c * complex(lam)))
+        cs = complex(self.c * scale)
+        for j in range(k):
+            out[j] = d
+            d = d * (cs / (j + 1))
+        return out
 
     def matfun(self, S):
         return sla.expm(self.c * np.asarray(S, dtype=complex))
@@ -113,6 +140,17 @@ class ISqrt(ScalarFun):
             out[j + 1] = d
         return out
 
+    def taylor(self, lam, k, scale=1.0):
+        # binomial series: tau_{j+1} = tau_j * scale*alpha/u * (1/2 - j)/(j + 1)
+        u = complex(self.alpha * complex(lam) + self.beta)
+        out = np.empty(k, dtype=np.complex128)
+        d = complex(1j * np.sqrt(u))
+        r = complex(scale * self.alpha / u)
+        for j in range(k):
+            out[j] = d
+            d = d * (r * ((0.5 - j) / (j + 1)))
+        return out
+
     def matfun(self, S):
         S = np.asarray(S, dtype=complex)
         return 1j * sla.sqrtm(self.alpha * S + self.beta * np.eye(S.shape[0]))
@@ -131,6 +169,9 @@ class Scaled(ScalarFun):
     def derivs(self, lam, k, scale=1.0):
         return self.c * self.f.derivs(lam, k, scale)
 
+    def taylor(self, lam, k, scale=1.0):
+        return self.c * self.f.taylor(lam, k, scale)
+
     def matfun(self, S):
         return self.c * self.f.matfun(S)
 
@@ -147,6 +188,9 @@ class Affine(ScalarFun):
     def derivs(self, lam, k, scale=1.0):
         # chain rule: d^j/dlam^j f(scale*lam+shift) = scale^j f^(j)(.)
         return self.f.derivs(self.scale * complex(lam) + self.shift, k, scale * self.scale)
+
+    def taylor(self, lam, k, scale=1.0):
+        return self.f.taylor(self.scale * complex(lam) + self.shift, k, scale * self.scale)
 
     def matfun(self, S):
         S = np.asarray(S, dtype=complex)
@@ -165,6 +209,9 @@ class Sum(ScalarFun):
 
     def derivs(self, lam, k, scale=1.0):
         return sum(f.derivs(lam, k, scale) for f in self.fs)
+
+    def taylor(self, lam, k, scale=1.0):
+        return sum(f.taylor(lam, k, scale) for f in self.fs)
 
     def matfun(self, S):
         return sum(f.matfun(S) for f in self.fs)
@@ -210,6 +257,27 @@ class WEPSqrt(ScalarFun):
             if j > 0:
                 fact *= j
             out[j] = 1j * t[j] * fact
+        out[0] += self.d0
+        return out
+
+    def taylor(self, lam, k, scale=1.0):
+        # g = sqrt(q) satisfies 2 q g' = q' g; with q = q0 + q1 h + q2 h^2 the coefficients of h^m give the three-term
+        # recurrence (m+1) q0 t_{m+1} = (1/2 - m) q1 t_m + (2 - m) q2 t_{m-1}.  Its other solution decays like the
+        # reciprocal of the farther root of q, so the forward recurrence is stable.
+        lam = complex(lam)
+        q0 = lam * lam + self.b * lam + self.c
+        a1 = (2 * lam + self.b) * scale / q0
+        a2 = scale * scale / q0
+        t = np.zeros(k, dtype=np.complex128)
+        if k == 0:
+            return t
+        t[0] = self._sqrt(lam)
+        tm1, tm = 0j, complex(t[0])
+        for m in range(k - 1):
+            nxt = ((0.5 - m) / (m + 1)) * a1 * tm + ((2.0 - m) / (m + 1)) * a2 * tm1
+            t[m + 1] = nxt
+            tm1, tm = tm, nxt
+        out = 1j * t
         out[0] += self.d0
         return out
 
