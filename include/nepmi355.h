@@ -404,12 +404,14 @@ int32_t nep_axpy(int64_t len, nep_cdouble alpha, const nep_cdouble* dx, nep_cdou
                  nep_stream stream);
 /* x *= alpha */
 int32_t nep_scal(int64_t len, nep_cdouble alpha, nep_cdouble* dx, nep_stream stream);
-/* ||x||_2 of len complex entries (synchronous) */
+/* ||x||_2 of len complex entries (synchronous).  The squares are summed unscaled (as in K6): entries whose squares overflow or
+ * underflow (beyond about 1e+-150) are outside the contract of nep_nrm2 / nep_colnorms / nep_rowmajor_colnorms. */
 int32_t nep_nrm2(int64_t len, const nep_cdouble* dx, double* h_out, nep_stream stream);
 /* column norms of a column-major rows x k block (synchronous) */
 int32_t nep_colnorms(int64_t rows, int32_t k, const nep_cdouble* dX, int64_t ldx, double* h_out,
                      nep_stream stream);
-/* dot products d_j = x_j^H y_j of the columns of two rows x k blocks (synchronous) */
+/* dot products d_j = x_j^H y_j of the columns of two rows x k blocks (synchronous); ldx = 0 (or ldy = 0) is accepted and means
+ * one column against k columns */
 int32_t nep_coldots(int64_t rows, int32_t k, const nep_cdouble* dX, int64_t ldx,
                     const nep_cdouble* dY, int64_t ldy, nep_cdouble* h_out, nep_stream stream);
 /* same without conjugation, d_j = x_j^T y_j: the bilinear sums `mat_sum` of the infinite Lanczos three-term recurrence
@@ -422,10 +424,10 @@ int32_t nep_coldotsu(int64_t rows, int32_t k, const nep_cdouble* dX, int64_t ldx
  *           `alpha = M\b` of the Sylvester-SMW preconditioner, waveguide_preconditioner.jl:378 (M^{-1} precomputed). */
 int32_t nep_gemv_hd(const nep_cdouble* dA, int64_t lda, int64_t rows, int32_t k, const nep_cdouble* dx,
                     const nep_cdouble* dd, nep_cdouble* dy, nep_stream stream);
-/* out[r] = sum_j A[r,j]*B[r,j] (column-major blocks, no conjugation) */
+/* out[r] = sum_j A[r,j]*B[r,j] (column-major blocks, no conjugation); lda, ldb >= rows, else NEP_ERR_ARG */
 int32_t nep_rowdot(int64_t rows, int32_t k, const nep_cdouble* dA, int64_t lda, const nep_cdouble* dB, int64_t ldb,
                    nep_cdouble* dout, nep_stream stream);
-/* A[r,j] *= B[r,j] (column-major blocks) */
+/* A[r,j] *= B[r,j] (column-major blocks); lda, ldb >= rows, else NEP_ERR_ARG; B may be A itself (squares in place) */
 int32_t nep_hadamard(int64_t rows, int32_t k, nep_cdouble* dA, int64_t lda, const nep_cdouble* dB, int64_t ldb,
                      nep_stream stream);
 /* column 2-norms of a ROW-major rows x k block (row stride ld); synchronous */

@@ -503,9 +503,8 @@ __global__ void k_rowdot(int64_t rows, int k, const cplx* __restrict__ A, int64_
         out[r] = acc;
     }
 }
-// A[r + j*lda] *= B[r + j*ldb]
-__global__ void k_hadamard(int64_t rows, int k, cplx* __restrict__ A, int64_t lda, const cplx* __restrict__ B,
-                           int64_t ldb) {
+// A[r + j*lda] *= B[r + j*ldb]   (B may be A itself: no __restrict__)
+__global__ void k_hadamard(int64_t rows, int k, cplx* A, int64_t lda, const cplx* B, int64_t ldb) {
     const int64_t total = rows * (int64_t)k;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = i % rows, j = i / rows;
@@ -790,7 +789,7 @@ int32_t nep_gemv_hd(const nep_cdouble* dA, int64_t lda, int64_t rows, int32_t k,
 
 int32_t nep_rowdot(int64_t rows, int32_t k, const nep_cdouble* dA, int64_t lda, const nep_cdouble* dB, int64_t ldb,
                    nep_cdouble* dout, nep_stream stream) {
-    ARGCHK(rows > 0 && k >= 1 && dA && dB && dout);
+    ARGCHK(rows > 0 && k >= 1 && dA && dB && dout && lda >= rows && ldb >= rows);
     hipLaunchKernelGGL(k_rowdot, dim3(grid_for(rows, 256)), dim3(256), 0, as_stream(stream), rows, (int)k,
                        (const cplx*)dA, lda, (const cplx*)dB, ldb, (cplx*)dout);
     LAUNCHCHK();
@@ -799,7 +798,7 @@ int32_t nep_rowdot(int64_t rows, int32_t k, const nep_cdouble* dA, int64_t lda, 
 
 int32_t nep_hadamard(int64_t rows, int32_t k, nep_cdouble* dA, int64_t lda, const nep_cdouble* dB, int64_t ldb,
                      nep_stream stream) {
-    ARGCHK(rows > 0 && k >= 1 && dA && dB);
+    ARGCHK(rows > 0 && k >= 1 && dA && dB && lda >= rows && ldb >= rows);
     hipLaunchKernelGGL(k_hadamard, dim3(grid_for(rows * k, 256)), dim3(256), 0, as_stream(stream), rows, (int)k,
                        (cplx*)dA, lda, (const cplx*)dB, ldb);
     LAUNCHCHK();

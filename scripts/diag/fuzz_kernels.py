@@ -9,6 +9,50 @@ def chk(name, err, tol, info):
     global bad
     if not (err <= tol):
         bad += 1; print("FAIL", name, err, info, flush=True)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "tests"))
+import primitive_checkers as pc, test_gpu_primitives as tg
+def prim_sweep(n, k, p, kk, mt):
+    """one exact case per primitive at the iteration's sizes (n rows, k / p / kk columns), padded leading dimensions"""
+    g = lambda *shape: pc.gint(rng, shape)
+    run = lambda name, **a: pc.BY_NAME[name].check(tg.ADAPTERS[name], pc.Case("fuzz", "n%d_k%d_p%d_kk%d" % (n, k, p, kk), "exact", lambda: a))
+    for name in ("nep_coldots", "nep_coldotsu"):
+        run(name, rows=n, k=kk, X=pc.colmajor_buf(g(n, kk), n + 1), ldx=n + 1, Y=pc.colmajor_buf(g(n, kk), n + 2), ldy=n + 2)
+    run("nep_colnorms", rows=n, k=kk, X=pc.colmajor_buf(g(n, kk), n + 1), ldx=n + 1)
+    run("nep_nrm2", len=n, x=g(n))
+    run("nep_rowmajor_colnorms", rows=n, k=kk, XT=pc.rowmajor_buf(g(n, kk), kk + 1), ld=kk + 1)
+    cols = rng.integers(0, kk, kk + 1).astype(np.int32)
+    run("nep_rowmajor_to_colmajor", rows=n, k=kk, src=pc.rowmajor_buf(g(n, kk), kk + 1), lds=kk + 1, cols=cols, ncols=len(cols),
+        dst=np.full((n + 1) * len(cols) + 1, pc.SENT), ldd=n + 1)
+    run("nep_rowdot", rows=n, k=k, A=pc.colmajor_buf(g(n, k), n + 1), lda=n + 1, B=pc.colmajor_buf(g(n, k), 2 * n), ldb=2 * n)
+    run("nep_hadamard", rows=n, k=k, A=pc.colmajor_buf(g(n, k), n + 1, fill=pc.SENT), lda=n + 1, B=pc.colmajor_buf(g(n, k), 2 * n), ldb=2 * n)
+    run("nep_axpy", len=n, alpha=complex(2, -3), x=np.append(g(n), pc.NAN), y=np.append(g(n), [pc.SENT] * 2))
+    run("nep_scal", len=n, alpha=complex(2, -3), x=np.append(g(n), [pc.SENT] * 2))
+    buf = np.full(2 * n * (k + 1) + 3, pc.SENT); buf[:n * k] = g(n * k)
+    run("nep_iar_shift_scale", n=n, k=k, buf=buf, src_off=0, dst_off=n * (k + 1) + 1)
+    N = int(rng.choice([0, 1, 2, 43]))
+    run("nep_rk_bw", n=n, N=N, wc=np.append(g(n * (N + 1)), pc.NAN), wc_off=0, c=g(N), Bw=np.full(n * (N + 1) + 2, pc.SENT), bw_off=0)
+    xy = np.append(g(n * (N + 1)), pc.SENT)
+    run("nep_block_recur", n=n, N=N, a=pc.gint(rng, N, -2, 2), b=rng.choice(np.array([0, 1, -1, 1j, -1j]), N).astype(complex), y=xy, y_off=0,
+        x=xy, x_off=0)
+    run("nep_gemv_h", V=pc.colmajor_buf(g(n, k), n + 3), ldv=n + 3, rows=n, k=k, w=np.append(g(n), pc.NAN))
+    for brm in (0, 1):
+        ldb = (p if brm else k) + 2
+        Bb = pc.rowmajor_buf(g(k, p), ldb, lead=3, trail=1) if brm else pc.colmajor_buf(g(k, p), ldb, lead=3, trail=1)
+        yrm = int(rng.integers(0, 2))
+        ldy = (p if yrm else n) + 1
+        run("nep_gemm_ts_dev", Z=pc.colmajor_buf(g(n, k), n + 1, lead=2), z_off=2, ldz=n + 1, rows=n, k=k, B=Bb, b_off=3, ldb=ldb, b_rowmajor=brm,
+            p=p, Y=np.full(1 + (n if yrm else p) * ldy + 1, pc.SENT), y_off=1, ldy=ldy, y_rowmajor=yrm)
+    ta, tb = int(rng.integers(0, 3)), int(rng.integers(0, 3))
+    m_, n_ = min(n, 130), p
+    A = g(m_, n) if ta == 0 else g(n, m_); B = g(n, n_) if tb == 0 else g(n_, n)
+    run("nep_zgemm_sk", transa=ta, transb=tb, m=m_, n=n_, k=n, alpha=complex(1, -2), A=pc.colmajor_buf(A, A.shape[0] + 1), lda=A.shape[0] + 1,
+        B=pc.colmajor_buf(B, B.shape[0] + 1), ldb=B.shape[0] + 1, beta=complex(2, 1), C=pc.colmajor_buf(g(m_, n_), m_ + 1, fill=pc.SENT), ldc=m_ + 1,
+        ksplit=int(rng.choice([1, 2, 7, 64])))
+    if n >= 8:
+        terms = pc.spmm_terms_matrices(min(n, 300), mt, bool(rng.integers(0, 2)), int(rng.integers(1 << 30)))
+        nn, pp = terms[0].shape[0], int(rng.choice([1, 7, 64, 65, 129, 200, 256]))
+        run("nep_spmm_terms", terms=terms, p=pp, XT=pc.rowmajor_buf(g(nn, pp * mt), pp * mt + 1), ldx=pp * mt + 1,
+            ZT=np.full(nn * (pp + 1) + 1, pc.SENT), ldz=pp + 1)
 for it in range(int(sys.argv[2]) if len(sys.argv) > 2 else 60):
     n = int(rng.choice([1, 2, 3, 5, 17, 64, 65, 257, 1000, 4099]))
     mt = int(rng.integers(1, 6))
@@ -66,4 +110,10 @@ for it in range(int(sys.argv[2]) if len(sys.argv) > 2 else 60):
             chk("K5", np.linalg.norm(A @ X - Bm), 1e-9 * np.linalg.norm(Bm), (n, nr, lu.tail, lu.mid_rows))
         except np.linalg.LinAlgError:
             pass
+    # ---- the driver-only primitives (BLAS-1 helpers, rk helpers, gemv_h, gemm_ts_dev, zgemm_sk, spmm_terms): Gaussian-integer
+    # operands on the same ragged sizes, bit-for-bit against NumPy (tests/primitive_checkers.py has the references)
+    try:
+        prim_sweep(n, k, p, kk, mt)
+    except AssertionError as e:
+        bad += 1; print("FAIL primitive", str(e)[:300], flush=True)
 print("done, failures:", bad)
