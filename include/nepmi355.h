@@ -356,7 +356,8 @@ int32_t nep_lu_set_plan_threads(int32_t n);
  * info[5]=bytes one solve with one right-hand side moves under the schedule in use (the ALGORITHMIC bytes of SURVEY.md
  * section 8d are (nnz(L)+nnz(U))*20 + 8(n+1) + 48n, computable from info[0..2]) */
 int32_t nep_lu_info(const nep_lu* lu, int64_t info[6]);
-/* schedule introspection.  Block schedule (default, trsv_ml.hip): out[0]=0, out[1]=kernel launches of the last solve,
+/* schedule introspection.  Block schedule (default, trsv_ml.hip): out[0]=rows of the dense apex (the top levels merged into one
+ * inverted block; 0 = none), out[1]=kernel launches of the last solve,
  * out[2]=out[3]=levels of the block partition, out[4]=levels whose coupling product is a separate launch (L+U),
  * out[5]=number of diagonal blocks, out[6]=rows covered by inverted blocks (= n), out[7]=largest block size.
  * Level schedule (NEP_LU_SCHED=old, and the fallback): out[0]=dense tail size T, out[1]=launches, out[2]=levels(L),
@@ -370,13 +371,16 @@ int32_t nep_lu_is_block_schedule(const nep_lu* lu, int32_t* out);
  * patterns have a dependency outside the elimination tree (the level schedule is used then). */
 int32_t nep_lu_analyze(int64_t n, int32_t csc, const int32_t* hLp, const int32_t* hLi, const int32_t* hUp,
                        const int32_t* hUi, int64_t out[8]);
-/* X = A^{-1} B for nrhs right-hand sides; dB, dX: n x nrhs column-major; dX may alias dB.
- * scale is applied to the result (iar/tiar use -1: y = -lin_solve(...), src/method_iar.jl:103). */
+/* X = A^{-1} B for nrhs right-hand sides; dB, dX: n x nrhs column-major; dX may alias dB (then ldx = ldb).
+ * scale is applied to the result (iar/tiar use -1: y = -lin_solve(...), src/method_iar.jl:103).
+ * ldb, ldx >= n: the rows n .. ld - 1 of a column are neither read nor written.  NEP_ERR_ARG, with nothing written, for
+ * nrhs < 1 (an empty block is not a no-op) or nrhs > 65535, a leading dimension below n, a NULL handle or buffer. */
 int32_t nep_lu_solve(nep_lu* lu, int32_t nrhs, const nep_cdouble* dB, int64_t ldb, nep_cdouble* dX,
                      int64_t ldx, double scale, nep_stream stream);
 
 /* X = scale * (Add + A^{-1} B): the update step of the iterative refinement (x + A^{-1} r, UMFPACK's solve behind
- * src/LinSolvers.jl:114-122) fused into the output permutation; dAdd may alias dX, NULL means zero. */
+ * src/LinSolvers.jl:114-122) fused into the output permutation; dAdd may alias dX, NULL means zero.  The argument checks of nep_lu_solve apply;
+ * ldadd >= n is required when dAdd is given and ignored when it is NULL. */
 int32_t nep_lu_solve_add(nep_lu* lu, int32_t nrhs, const nep_cdouble* dB, int64_t ldb, const nep_cdouble* dAdd,
                          int64_t ldadd, nep_cdouble* dX, int64_t ldx, double scale, nep_stream stream);
 
@@ -520,7 +524,7 @@ int32_t nep_lu_refac_analyze(int64_t n, const int32_t* Lp, const int32_t* Li, co
 int32_t nep_lu_refac_info(const nep_lu_refac* r, int64_t out[6]);
 /* The "wide" levels (top of the elimination tree: few blocks, one long chain of pivots each) are factorised in panels of P
  * consecutive pivots per launch (round 4; NEP_LU_WIDE_P = 1..4, default 4; 1 = one launch per pivot step as before):
- * out[0] = P, [1] = pivot steps of the wide levels, [2] = launches they take per factorisation, [3] = destination records,
+ * out[0] = P (1 for a plan whose wide levels hold no product: nothing to put in panels), [1] = pivot steps of the wide levels, [2] = launches they take per factorisation, [3] = destination records,
  * [4] = deferred products (updates into a panel's own later rows / columns, applied at the end of the level). */
 int32_t nep_lu_refac_wide_info(const nep_lu_refac* r, int64_t out[5]);
 /* out[0] = hash of the plan arrays as they sit on the device (the quantity nep_lu_refac_analyze returns in out[7] for the host

@@ -1362,7 +1362,8 @@ static int ml_numeric_dev(MLFactor* F, const cplx* d_Lx, const cplx* d_Ux, hipSt
         hipEvent_t ev; HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         HIPCHK(hipEventRecord(ev, producer)); HIPCHK(hipStreamWaitEvent(bst, ev, 0)); (void)hipEventDestroy(ev);
     }
-    const int gl = (int)std::min<int64_t>((S->nnzL + 255) / 256, 4096), gu = (int)std::min<int64_t>((S->nnzU + 255) / 256, 4096);
+    // (at least one workgroup: L of a transposed pair has no stored entry when U is diagonal, and a grid of 0 is a launch error)
+    const int gl = (int)std::max<int64_t>(1, std::min<int64_t>((S->nnzL + 255) / 256, 4096)), gu = (int)std::max<int64_t>(1, std::min<int64_t>((S->nnzU + 255) / 256, 4096));
     hipLaunchKernelGGL(k_ml_gather, dim3(gl), dim3(256), 0, bst, S->nnzL, (const int32_t*)S->L.d_map, d_Lx, F->d_vals, oL, oLb, oD);
     LAUNCHCHK();
     hipLaunchKernelGGL(k_ml_gather, dim3(gu), dim3(256), 0, bst, S->nnzU, (const int32_t*)S->U.d_map, d_Ux, F->d_vals, oU, oUb, oD);
@@ -1456,7 +1457,8 @@ int ml_create_from_sym_batch(MLSym* S, int B, const nep_cdouble* const* d_Lx, co
     }
     cplx* const* t_vals = (cplx* const*)d_tab; cplx* const* t_ixL = (cplx* const*)(d_tab + B); cplx* const* t_ixU = (cplx* const*)(d_tab + 2 * (size_t)B);
     const cplx* const* t_sL = (const cplx* const*)(d_tab + 3 * (size_t)B); const cplx* const* t_sU = (const cplx* const*)(d_tab + 4 * (size_t)B);
-    const int gl = (int)std::min<int64_t>((S->nnzL + 255) / 256, 4096), gu = (int)std::min<int64_t>((S->nnzU + 255) / 256, 4096);
+    // (at least one workgroup: L of a transposed pair has no stored entry when U is diagonal, and a grid of 0 is a launch error)
+    const int gl = (int)std::max<int64_t>(1, std::min<int64_t>((S->nnzL + 255) / 256, 4096)), gu = (int)std::max<int64_t>(1, std::min<int64_t>((S->nnzU + 255) / 256, 4096));
     hipLaunchKernelGGL(k_ml_gather, dim3(gl, B), dim3(256), 0, bst, S->nnzL, (const int32_t*)S->L.d_map, (const cplx*)nullptr, (cplx*)nullptr, oL, oLb, oD, t_vals, t_sL);
     hipLaunchKernelGGL(k_ml_gather, dim3(gu, B), dim3(256), 0, bst, S->nnzU, (const int32_t*)S->U.d_map, (const cplx*)nullptr, (cplx*)nullptr, oU, oUb, oD, t_vals, t_sU);
     MLBatchTab tl; tl.vals = t_vals; tl.ix = t_ixL; tl.off_bx = oLb; tl.off_diag = 0;
