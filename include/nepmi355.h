@@ -103,6 +103,49 @@ int32_t nep_k1_set_mode(int32_t mode);
  * (default), 2 = whenever the footprint tiles allow it, -1 = the environment variable NEP_K2_SP decides.  Reference: the residual of
  * all Ritz pairs, src/errmeasure.jl:128-130,186-190. */
 int32_t nep_k2_set_sp_mode(int32_t mode);
+/* Dispatch query: what the entry points below would launch for this handle and k under the current modes and environment.
+ * Host-only, launches nothing; it evaluates the very predicates the launchers call, so it cannot drift from them (tests state
+ * with it which kernel instantiation a case covered).
+ * op: NEP_PLAN_K1 nep_mlincomb[_dev]; NEP_PLAN_K2_NORMS nep_resid_batch[_dev] / nep_resid_split_dev; NEP_PLAN_K2_BLOCK
+ * nep_resid_block; NEP_PLAN_K2_CM nep_resid_batch_cm_dev.  The row-major K2 forms work in column panels of
+ * P = min(256, max(1, 3072 / mt)) columns: the answer describes the first panel (min(k, P) columns, row stride ldq = k assumed
+ * for the 32-bit-offset test of k_spmm_rm_g); a narrower last panel may choose differently and is queried with its own k.
+ *   info[0] kernel, NEP_PLAN_K_* below
+ *   info[1] value bytes of the stored matrices (8 | 16)
+ *   info[2] terms unrolled in the kernel (template parameter M of the tiled kernels and of k_vc: min(mt, 4) -- k_vc takes the
+ *           terms four at a time and the remainder in a last launch; mt elsewhere)
+ *   info[3] flags, NEP_PLAN_F_* below
+ *   info[4] threads per workgroup of the matrix kernel
+ *   info[5] lanes per row (CSR kernels of K1; 64 = one row per lane of a SELL slice), 64-column chunks per row
+ *           (k_spmm_rm[_g]) or columns per tile panel (tiled K2)
+ *   info[6] flush mask of the slot layout (super-panel kernels: 0x80 one term, 0xD0 the 5 + 2 + 1 layout, 0xFF any other);
+ *           NEP_PLAN_K_VC_SPMV: rows per workgroup of k_vc (16 | 32 | 64); 0 elsewhere
+ *   info[7] number of column panels (passes over the matrix) of the call
+ * NEP_ERR_UNSUPPORTED (info all zero) where the entry point itself would refuse: NEP_PLAN_K2_CM without tiles or with mt > 4.
+ * NEP_ERR_ARG: k < 1, unknown op, NEP_PLAN_K2_BLOCK with k > 256. */
+#define NEP_PLAN_K1 0
+#define NEP_PLAN_K2_NORMS 1
+#define NEP_PLAN_K2_BLOCK 2
+#define NEP_PLAN_K2_CM 3
+#define NEP_PLAN_K_SPMV_FOLD 1      /* k = 1: k_spmv_fold<lanes> / k_spmv_sell<fold> */
+#define NEP_PLAN_K_SPMV_KFUSED 2    /* 2 <= k <= 16: k_spmv_kfused<lanes> / k_spmv_sell_kfused<k> */
+#define NEP_PLAN_K_VC_SPMV 3        /* k_vc<M, rows> per four terms, then k_spmv<lanes> / k_spmv_sell */
+#define NEP_PLAN_K_TILE_MLINCOMB 4  /* k_tile_mlincomb<M, non-temporal, prefetch> */
+#define NEP_PLAN_K_SPMM_RM_G 5      /* k_spmm_rm_g<chunks = 1, 2> */
+#define NEP_PLAN_K_SPMM_RM 6        /* k_spmm_rm<chunks = 1..4> */
+#define NEP_PLAN_K_TILE_RESID 7     /* k_tile_resid<M, panel 4 | 8, non-temporal> */
+#define NEP_PLAN_K_TILE_RESID_SP 8  /* k_tile_resid_sp<layout, threads, flush mask> */
+#define NEP_PLAN_K_TILE_RESID_SPP 9 /* k_tile_resid_spp: the persistent form */
+#define NEP_PLAN_K_TILE_RESID_CM 10 /* k_tile_resid_cm<M, panel 2 | 4 | 8, non-temporal> */
+#define NEP_PLAN_K_TILE_RESID_SP4 11 /* k_tile_resid_sp4: ring of four half-tiles, column-major only */
+#define NEP_PLAN_F_SELL 1
+#define NEP_PLAN_F_NT 2             /* non-temporal loads of the matrix entries */
+#define NEP_PLAN_F_PREFETCH 4       /* register prefetch of the next block's entries */
+#define NEP_PLAN_F_COLSPLIT 8       /* the k columns split over thread groups */
+#define NEP_PLAN_F_PERSISTENT 16
+#define NEP_PLAN_F_RING 32
+#define NEP_PLAN_F_XCD_ROWS 64      /* rows dealt to the XCDs in contiguous ranges (k_spmm_rm[_g]) */
+int32_t nep_spmf_plan(const nep_spmf* s, int32_t op, int32_t k, int64_t info[8]);
 int32_t nep_csc_to_csr(int64_t n, const int64_t* colptr, const int64_t* rowval, const void* nzval,
                        int32_t val_is_complex, int32_t one_based, int32_t* rowptr, int32_t* colind,
                        void* vals);
@@ -163,20 +206,27 @@ int32_t nep_resid_batch_dev(nep_spmf* s, int32_t k, const nep_cdouble* hF, const
 /* K2 for operators with an extra term on their last rows (WEP: dense corner block on the 2 nz boundary rows,
  * src/gallery_extra/waveguide/Waveguide.jl:351-374): one pass gives d_out (device, 2k doubles) = squared column norms of the
  * SPMF residual over rows [0, row0) and of Q over all rows, and dRT_tail ((n - row0) x k row-major, ld ldt) = the residual
- * rows [row0, n); the caller adds its term to the tail and the tail's norms to d_out. */
+ * rows [row0, n); the caller adds its term to the tail and the tail's norms to d_out.  0 <= row0 <= n (row0 = n: no tail rows,
+ * row0 = 0: no rows in the residual norms), ldt >= k, dRT_tail not NULL even when it has no rows; d_out in the panel layout of
+ * nep_resid_batch_dev; the columns k .. ldt - 1 of the tail are not written.  NEP_ERR_ARG otherwise, nothing launched. */
 int32_t nep_resid_split_dev(nep_spmf* s, int32_t k, const nep_cdouble* hF, const nep_cdouble* dQT, int64_t ldq, int64_t row0,
                             double* d_out, nep_cdouble* dRT_tail, int64_t ldt, nep_stream stream);
 /* K2 with a COLUMN-major Ritz block (n x k, column s at dQ + s ldq, what nep_gemm_ts writes with y_rowmajor = 0): at
  * waveguide scale the panel loads of the tiled kernel are then contiguous per column and every byte of Q crosses HBM once
  * (csrc/spmv_tile.hip k_tile_resid_cm).  d_out: 2k squared norms (device).  row0 < 0: whole residual in the norms; row0 >= 0:
  * rows [0, row0) in the norms, rows [row0, n) written to dR_tail ((n - row0) x k column-major, ld ldt) as in
- * nep_resid_split_dev.  NEP_ERR_UNSUPPORTED when the matrix has no footprint tiles or more than 4 terms. */
+ * nep_resid_split_dev.  NEP_ERR_UNSUPPORTED when the matrix has no footprint tiles, more than 4 terms, or a largest column
+ * footprint above 1200 (eight tile columns of it have to fit 150 KiB of LDS; nep_spmf_tile_info, info[1]).  Any k >= 1: the
+ * kernels walk the columns in panels and read the coefficients from device memory, so there is no upper limit on k (k = 300 is
+ * tested); d_out is ONE block of 2k doubles, ||r_s||^2 at d_out[s] and ||q_s||^2 at d_out[k + s], whatever k.
+ * NEP_ERR_ARG, nothing launched: k < 1, ldq < n, row0 > n, or row0 >= 0 with dR_tail NULL or ldt < n - row0. */
 int32_t nep_resid_batch_cm_dev(nep_spmf* s, int32_t k, const nep_cdouble* hF, const nep_cdouble* dQ, int64_t ldq, int64_t row0,
                                double* d_out, nep_cdouble* dR_tail, int64_t ldt, nep_stream stream);
 
 /* same residuals, but the block R^T (row-major, row stride ldr >= k) is written instead of its norms --
  * for NEPs with an extra non-SPMF term (the WEP corner, src/gallery_extra/waveguide/Waveguide.jl:351-374)
- * whose contribution is added before the norms are taken.  Asynchronous. */
+ * whose contribution is added before the norms are taken.  Asynchronous.  1 <= k <= 256 (NEP_ERR_ARG above: callers split the
+ * columns themselves); the columns k .. ldr - 1 of a row of dRT are not written, the columns k .. ldq - 1 of dQT never read. */
 int32_t nep_resid_block(nep_spmf* s, int32_t k, const nep_cdouble* hF, const nep_cdouble* dQT, int64_t ldq,
                         nep_cdouble* dRT, int64_t ldr, nep_stream stream);
 

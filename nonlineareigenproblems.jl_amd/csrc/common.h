@@ -190,6 +190,7 @@ int nep_tiles_mlincomb(const NepTiles* t, int k, const cplx* dC, int64_t ldc, co
                        hipStream_t st);
 // K2 on the tiles: R = residual block of k Ritz pairs (row-major Q), column norms as [nblk][2][k] partials and / or R itself
 int nep_tiles_nblk(const NepTiles* t);
+void nep_tiles_plan(const NepTiles* t, int op, int k, int cm, int64_t p[6]);
 bool nep_tiles_resid_ok(const NepTiles* t, int k);
 bool nep_tiles_resid_cm_ok(const NepTiles* t, int k);
 int nep_tiles_resid_cm(const NepTiles* t, int k, const cplx* dF, const cplx* Q, int64_t ldq, cplx* R, int64_t ldr, double* partial,

@@ -636,13 +636,18 @@ static int launch_vc_rows(const nep_spmf* s, int k, const cplx* dC, int64_t ldc,
     }
     return NEP_OK;
 }
-static int launch_vc(const nep_spmf* s, int k, const cplx* dC, int64_t ldc, const cplx* V, int64_t ldv, hipStream_t st, cplx* shift_dst = nullptr) {
+// rows per workgroup of k_vc (shared with nep_spmf_plan)
+static int vc_rows(const nep_spmf* s) {
     static const int force = getenv("NEP_VC_ROWS") ? atoi(getenv("NEP_VC_ROWS")) : 0;
-    if (force == 16) return launch_vc_rows<16>(s, k, dC, ldc, V, ldv, st, shift_dst);
-    if (force == 32) return launch_vc_rows<32>(s, k, dC, ldc, V, ldv, st, shift_dst);
-    if (force == 64) return launch_vc_rows<64>(s, k, dC, ldc, V, ldv, st, shift_dst);
-    if (s->n >= 65536) return launch_vc_rows<64>(s, k, dC, ldc, V, ldv, st, shift_dst);
-    return launch_vc_rows<32>(s, k, dC, ldc, V, ldv, st, shift_dst);
+    if (force == 16 || force == 32 || force == 64) return force;
+    return s->n >= 65536 ? 64 : 32;
+}
+static int launch_vc(const nep_spmf* s, int k, const cplx* dC, int64_t ldc, const cplx* V, int64_t ldv, hipStream_t st, cplx* shift_dst = nullptr) {
+    switch (vc_rows(s)) {
+        case 16: return launch_vc_rows<16>(s, k, dC, ldc, V, ldv, st, shift_dst);
+        case 64: return launch_vc_rows<64>(s, k, dC, ldc, V, ldv, st, shift_dst);
+        default: return launch_vc_rows<32>(s, k, dC, ldc, V, ldv, st, shift_dst);
+    }
 }
 
 // The same for k <= 64 with the dependent round trips of a row taken apart (round 3, late): k_spmm_rm waits for the gathered row
@@ -775,21 +780,36 @@ __global__ __launch_bounds__(256) void k_spmm_rm_g(const int32_t* __restrict__ r
     }
 }
 
+// kernel form of a row-major SpMM pass (shared with nep_spmf_plan): 64-column chunks per row, the grouped-gather kernel for up to
+// two chunks while every element offset into XT fits 32 bits, rows dealt to the XCDs in contiguous ranges on large matrices
+struct SpmmShape { int nch, grouped, xcd_rows; };
+static SpmmShape spmm_shape(const nep_spmf* s, int k, int64_t ldx, int xoff, int grid) {
+    static const int xcd_env = getenv("NEP_SPMM_XCD") ? atoi(getenv("NEP_SPMM_XCD")) : 1;
+    static const int grouped = getenv("NEP_SPMM_GROUPED") ? atoi(getenv("NEP_SPMM_GROUPED")) : 1;
+    SpmmShape sh;
+    sh.nch = (k + 63) / 64;
+    sh.xcd_rows = (xcd_env && s->n >= 65536 && grid >= 64) ? 1 : 0;      // small matrices sit in every L2 anyway
+    sh.grouped = (sh.nch <= 2 && grouped &&
+                  (uint64_t)s->n * (uint64_t)ldx + (uint64_t)s->mt * (uint64_t)(xoff < 0 ? -xoff : xoff) < (1ull << 32)) ? 1 : 0;
+    return sh;
+}
+// workgroups of a pass: the norm forms keep their per-workgroup partial sums small, the block forms fill the device
+static int spmm_grid(const nep_spmf* s, bool norms) { return (int)std::min<int64_t>((s->n + 3) / 4, norms ? 2048 : 4096); }
+
 template <typename VT>
 static int launch_spmm(const nep_spmf* s, int k, const cplx* dF, const cplx* XT, int64_t ldx, int xoff,
                        cplx* ZT, int64_t ldz, double* partial, int grid, hipStream_t st, int64_t split_row = -1) {
-    const int nch = (k + 63) / 64;
+    const SpmmShape sh = spmm_shape(s, k, ldx, xoff, grid);
+    const int nch = sh.nch;
     const size_t shm = (dF ? (size_t)s->mt * k * sizeof(cplx) : 0) + (size_t)4 * 2 * nch * 64 * sizeof(double);
     const VT* vals = (const VT*)s->d_vals;
-    static const int xcd_env = getenv("NEP_SPMM_XCD") ? atoi(getenv("NEP_SPMM_XCD")) : 1;
-    const int xcd_rows = (xcd_env && s->n >= 65536 && grid >= 64) ? 1 : 0;      // small matrices sit in every L2 anyway
+    const int xcd_rows = sh.xcd_rows;
 #define SPMM_CASE(N)                                                                                   \
     case N:                                                                                            \
         hipLaunchKernelGGL((k_spmm_rm<N, VT>), dim3(grid), dim3(256), shm, st, s->d_rowptr, s->d_idx,  \
                            vals, s->n, s->mt, k, dF, XT, ldx, xoff, ZT, ldz, partial, split_row, xcd_rows); \
         break;
-    static const int grouped = getenv("NEP_SPMM_GROUPED") ? atoi(getenv("NEP_SPMM_GROUPED")) : 1;
-    if (nch <= 2 && grouped && (uint64_t)s->n * (uint64_t)ldx + (uint64_t)s->mt * (uint64_t)(xoff < 0 ? -xoff : xoff) < (1ull << 32)) {
+    if (sh.grouped) {
 if (nch == 1) hipLaunchKernelGGL((k_spmm_rm_g<VT, 1>), dim3(grid), dim3(256), shm, st, s->d_rowptr, s->d_idx, vals, s->n, s->mt, k, dF, XT, ldx,
                                          xoff, ZT, ldz, partial, split_row, xcd_rows);
         else hipLaunchKernelGGL((k_spmm_rm_g<VT, 2>), dim3(grid), dim3(256), shm, st, s->d_rowptr, s->d_idx, vals, s->n, s->mt, k, dF, XT, ldx,
@@ -995,6 +1015,28 @@ static bool use_sp_k2(const nep_spmf* s, int k, int cm) {
     return m == 2 || s->d_sell_ptr != nullptr;
 }
 
+// the kernel of one K1 call / of one row-major K2 panel / of a column-major K2 call: decided here, for the launchers and for
+// nep_spmf_plan alike
+enum { K1_TILE, K1_FOLD, K1_KFUSED, K1_VC };
+static int k1_choice(const nep_spmf* s, int k) {
+    if (use_tiles(s, k)) return K1_TILE;
+    if (k == 1) return K1_FOLD;
+    if (k <= fuse_max(s) && (size_t)s->mt * k * sizeof(cplx) <= 48 * 1024) return K1_KFUSED;
+    return K1_VC;
+}
+enum { K2_SP, K2_TILE, K2_SPMM, K2_CM, K2_NONE };
+static int k2_choice(const nep_spmf* s, int kk) {
+    if (use_sp_k2(s, kk, 0)) return K2_SP;
+    if (use_tiles_k2(s, kk)) return K2_TILE;
+    return K2_SPMM;
+}
+static int k2_cm_choice(const nep_spmf* s, int k) {
+    if (!s->tiles || !nep_tiles_resid_cm_ok(s->tiles, k)) return K2_NONE;
+    // (up to two panels the older kernel -- many short-lived workgroups per CU -- hides a block's start-up better: 69 against 77 us at k = 8)
+    static const int sp_cm_kmin = getenv("NEP_K2_SP_CM_KMIN") ? atoi(getenv("NEP_K2_SP_CM_KMIN")) : 9;
+    return (use_sp_k2(s, k, 1) && (k >= sp_cm_kmin || g_k2_sp_mode == 2)) ? K2_SP : K2_CM;
+}
+
 int32_t nep_spmf_tile_info(const nep_spmf* s, int64_t info[8]) {
     ARGCHK(s && info);
     for (int i = 0; i < 8; ++i) info[i] = 0;
@@ -1037,6 +1079,24 @@ int32_t nep_spmf_info(const nep_spmf* s, int64_t info[6]) {
     return NEP_OK;
 }
 
+// K1 with the coefficient block on the device (column stride ldc): the body of nep_mlincomb and nep_mlincomb_dev
+static int mlincomb_launch(nep_spmf* s, int k, const cplx* dC, int64_t ldc, const cplx* dV, int64_t ldv, cplx* dz, hipStream_t st) {
+    switch (k1_choice(s, k)) {
+        case K1_TILE: return nep_tiles_mlincomb(s->tiles, k, dC, ldc, dV, ldv, dz, nullptr, st);
+        case K1_FOLD:
+            if (s->valbytes == 8) return launch_spmv_fold<double>(s, dV, dC, ldc, dz, st);
+            return launch_spmv_fold<cplx>(s, dV, dC, ldc, dz, st);
+        case K1_KFUSED:
+            if (s->valbytes == 8) return launch_spmv_kfused<double>(s, k, dV, ldv, dC, ldc, dz, st);
+            return launch_spmv_kfused<cplx>(s, k, dV, ldv, dC, ldc, dz, st);
+        default: break;
+    }
+    const int rc = launch_vc(s, k, dC, ldc, dV, ldv, st);
+    if (rc) return rc;
+    if (s->valbytes == 8) return launch_spmv<double>(s, s->d_WT, dz, st);
+    return launch_spmv<cplx>(s, s->d_WT, dz, st);
+}
+
 int32_t nep_mlincomb(nep_spmf* s, int32_t k, const nep_cdouble* hC, const nep_cdouble* dV, int64_t ldv,
                      nep_cdouble* dz, nep_stream stream) {
     ARGCHK(s && hC && dV && dz);
@@ -1049,20 +1109,7 @@ int32_t nep_mlincomb(nep_spmf* s, int32_t k, const nep_cdouble* hC, const nep_cd
     // the pinned ring protects the host side
     rc = s->ring.upload(s->coef.dptr, hC, cbytes, st);
     if (rc) return rc;
-    if (use_tiles(s, k))
-        return nep_tiles_mlincomb(s->tiles, k, (const cplx*)s->coef.dptr, k, (const cplx*)dV, ldv, (cplx*)dz, nullptr, st);
-    if (k == 1) {
-        if (s->valbytes == 8) return launch_spmv_fold<double>(s, (const cplx*)dV, (const cplx*)s->coef.dptr, 1, (cplx*)dz, st);
-        return launch_spmv_fold<cplx>(s, (const cplx*)dV, (const cplx*)s->coef.dptr, 1, (cplx*)dz, st);
-    }
-    if (k <= fuse_max(s) && (size_t)s->mt * k * sizeof(cplx) <= 48 * 1024) {
-        if (s->valbytes == 8) return launch_spmv_kfused<double>(s, k, (const cplx*)dV, ldv, (const cplx*)s->coef.dptr, k, (cplx*)dz, st);
-        return launch_spmv_kfused<cplx>(s, k, (const cplx*)dV, ldv, (const cplx*)s->coef.dptr, k, (cplx*)dz, st);
-    }
-    rc = launch_vc(s, k, (const cplx*)s->coef.dptr, k, (const cplx*)dV, ldv, st);
-    if (rc) return rc;
-    if (s->valbytes == 8) return launch_spmv<double>(s, s->d_WT, (cplx*)dz, st);
-    return launch_spmv<cplx>(s, s->d_WT, (cplx*)dz, st);
+    return mlincomb_launch(s, k, (const cplx*)s->coef.dptr, k, (const cplx*)dV, ldv, (cplx*)dz, st);
 }
 
 int32_t nep_mlincomb_dev(nep_spmf* s, int32_t k, const nep_cdouble* dC, int64_t ldc, const nep_cdouble* dV,
@@ -1070,20 +1117,7 @@ int32_t nep_mlincomb_dev(nep_spmf* s, int32_t k, const nep_cdouble* dC, int64_t 
     ARGCHK(s && dC && dV && dz);
     ARGCHK(k >= 1 && ldv >= s->n && ldc >= k);
     hipStream_t st = as_stream(stream);
-    if (use_tiles(s, k))
-        return nep_tiles_mlincomb(s->tiles, k, (const cplx*)dC, ldc, (const cplx*)dV, ldv, (cplx*)dz, nullptr, st);
-    if (k == 1) {
-        if (s->valbytes == 8) return launch_spmv_fold<double>(s, (const cplx*)dV, (const cplx*)dC, ldc, (cplx*)dz, st);
-        return launch_spmv_fold<cplx>(s, (const cplx*)dV, (const cplx*)dC, ldc, (cplx*)dz, st);
-    }
-    if (k <= fuse_max(s) && (size_t)s->mt * k * sizeof(cplx) <= 48 * 1024) {
-        if (s->valbytes == 8) return launch_spmv_kfused<double>(s, k, (const cplx*)dV, ldv, (const cplx*)dC, ldc, (cplx*)dz, st);
-        return launch_spmv_kfused<cplx>(s, k, (const cplx*)dV, ldv, (const cplx*)dC, ldc, (cplx*)dz, st);
-    }
-    int rc = launch_vc(s, k, (const cplx*)dC, ldc, (const cplx*)dV, ldv, st);
-    if (rc) return rc;
-    if (s->valbytes == 8) return launch_spmv<double>(s, s->d_WT, (cplx*)dz, st);
-    return launch_spmv<cplx>(s, s->d_WT, (cplx*)dz, st);
+    return mlincomb_launch(s, k, (const cplx*)dC, ldc, (const cplx*)dV, ldv, (cplx*)dz, st);
 }
 
 // nep_mlincomb_dev for iar's step: when the coefficient product runs as its own kernel (k_vc) the block shift of the basis
@@ -1091,11 +1125,12 @@ int32_t nep_mlincomb_dev(nep_spmf* s, int32_t k, const nep_cdouble* dC, int64_t 
 int nep_mlincomb_dev_shift(nep_spmf* s, int32_t k, const nep_cdouble* dC, int64_t ldc, const nep_cdouble* dV, int64_t ldv,
                            nep_cdouble* dz, nep_cdouble* d_shift, int32_t* folded, hipStream_t st) {
     *folded = 0;
-    if (use_tiles(s, k) && !getenv("NEP_NO_SHIFT_FOLD")) {      // one launch: coefficient product, SpMV and the block shift
+    const int ch = k1_choice(s, k);
+    if (ch == K1_TILE && !getenv("NEP_NO_SHIFT_FOLD")) {      // one launch: coefficient product, SpMV and the block shift
         *folded = 1;
         return nep_tiles_mlincomb(s->tiles, k, (const cplx*)dC, ldc, (const cplx*)dV, ldv, (cplx*)dz, (cplx*)d_shift, st);
     }
-    if (k == 1 || (k <= fuse_max(s) && (size_t)s->mt * k * sizeof(cplx) <= 48 * 1024) || getenv("NEP_NO_SHIFT_FOLD"))
+    if (ch != K1_VC || getenv("NEP_NO_SHIFT_FOLD"))
         return nep_mlincomb_dev(s, k, dC, ldc, dV, ldv, dz, (nep_stream)st);
     int rc = launch_vc(s, k, (const cplx*)dC, ldc, (const cplx*)dV, ldv, st, (cplx*)d_shift);
     if (rc) return rc;
@@ -1171,9 +1206,10 @@ static int resid_panels(nep_spmf* s, int32_t k, const nep_cdouble* hF, const nep
         if (rc) return rc;
         rc = s->ring.upload(s->coef.dptr, hF + (size_t)j0 * s->mt, cbytes, st);
         if (rc) return rc;
-        const bool sp = use_sp_k2(s, kk, 0);
-        const bool tiled = sp || use_tiles_k2(s, kk);
-        int grid = tiled ? nep_tiles_nblk(s->tiles) : (int)std::min<int64_t>((s->n + 3) / 4, 2048);
+        const int ch = k2_choice(s, kk);
+        const bool sp = ch == K2_SP;
+        const bool tiled = ch != K2_SPMM;
+        int grid = tiled ? nep_tiles_nblk(s->tiles) : spmm_grid(s, true);
         rc = s->part.ensure(((size_t)grid * 2 * kk + 2 * kk) * sizeof(double));
         if (rc) return rc;
         double* partial = (double*)s->part.dptr;
@@ -1235,7 +1271,8 @@ int32_t nep_resid_batch_cm_dev(nep_spmf* s, int32_t k, const nep_cdouble* hF, co
                                double* d_out, nep_cdouble* dR_tail, int64_t ldt, nep_stream stream) {
     ARGCHK(s && hF && dQ && d_out);
     ARGCHK(k >= 1 && ldq >= s->n && (row0 < 0 || (dR_tail && row0 <= s->n && ldt >= s->n - row0)));
-    if (!s->tiles || !nep_tiles_resid_cm_ok(s->tiles, k)) { nep_set_error("column-major K2: no footprint tiles for this matrix / k"); return NEP_ERR_UNSUPPORTED; }
+    const int ch = k2_cm_choice(s, k);
+    if (ch == K2_NONE) { nep_set_error("column-major K2: no footprint tiles for this matrix / k"); return NEP_ERR_UNSUPPORTED; }
     hipStream_t st = as_stream(stream);
     const size_t cbytes = (size_t)k * s->mt * sizeof(cplx);
     int rc = s->coef.ensure(cbytes);
@@ -1246,9 +1283,7 @@ int32_t nep_resid_batch_cm_dev(nep_spmf* s, int32_t k, const nep_cdouble* hF, co
     rc = s->part.ensure((size_t)grid * 2 * k * sizeof(double));
     if (rc) return rc;
     double* partial = (double*)s->part.dptr;
-    // (up to two panels the older kernel -- many short-lived workgroups per CU -- hides a block's start-up better: 69 against 77 us at k = 8)
-    static const int sp_cm_kmin = getenv("NEP_K2_SP_CM_KMIN") ? atoi(getenv("NEP_K2_SP_CM_KMIN")) : 9;
-    if (use_sp_k2(s, k, 1) && (k >= sp_cm_kmin || g_k2_sp_mode == 2))
+    if (ch == K2_SP)
         rc = nep_tiles_resid_sp(s->tiles, k, (const cplx*)s->coef.dptr, (const cplx*)dQ, ldq, 1, (cplx*)dR_tail, ldt, partial, row0 < 0 ? -1 : row0, st);
     else
         rc = nep_tiles_resid_cm(s->tiles, k, (const cplx*)s->coef.dptr, (const cplx*)dQ, ldq, (cplx*)dR_tail, ldt, partial, row0 < 0 ? -1 : row0, st);
@@ -1268,19 +1303,56 @@ int32_t nep_resid_block(nep_spmf* s, int32_t k, const nep_cdouble* hF, const nep
     if (rc) return rc;
     rc = s->ring.upload(s->coef.dptr, hF, cbytes, st);
     if (rc) return rc;
-    int grid = (int)std::min<int64_t>((s->n + 3) / 4, 4096);
+    int grid = spmm_grid(s, false);
     const int32_t P = resid_panel_width(s->mt);
     for (int32_t j0 = 0; j0 < k; j0 += P) {
         const int32_t kk = std::min(P, k - j0);
         const cplx* F = (const cplx*)s->coef.dptr + (size_t)j0 * s->mt;
         const cplx* Q = (const cplx*)dQT + j0;
         cplx* R = (cplx*)dRT + j0;
-        if (use_sp_k2(s, kk, 0)) rc = nep_tiles_resid_sp(s->tiles, kk, F, Q, ldq, 0, R, ldr, nullptr, -1, st);
-        else if (use_tiles_k2(s, kk)) rc = nep_tiles_resid(s->tiles, kk, F, Q, ldq, R, ldr, nullptr, -1, st);
+        const int ch = k2_choice(s, kk);
+        if (ch == K2_SP) rc = nep_tiles_resid_sp(s->tiles, kk, F, Q, ldq, 0, R, ldr, nullptr, -1, st);
+        else if (ch == K2_TILE) rc = nep_tiles_resid(s->tiles, kk, F, Q, ldq, R, ldr, nullptr, -1, st);
         else if (s->valbytes == 8) rc = launch_spmm<double>(s, kk, F, Q, ldq, 0, R, ldr, nullptr, grid, st);
         else rc = launch_spmm<cplx>(s, kk, F, Q, ldq, 0, R, ldr, nullptr, grid, st);
         if (rc) return rc;
     }
+    return NEP_OK;
+}
+
+// dispatch query (include/nepmi355.h): the choices above, reported instead of launched
+int32_t nep_spmf_plan(const nep_spmf* s, int32_t op, int32_t k, int64_t info[8]) {
+    ARGCHK(s && info);
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    ARGCHK(k >= 1 && op >= NEP_PLAN_K1 && op <= NEP_PLAN_K2_CM && !(op == NEP_PLAN_K2_BLOCK && k > 256));
+    int64_t tp[6] = {0, 0, 0, 0, 0, 0};
+    const int sell = s->d_sell_ptr ? NEP_PLAN_F_SELL : 0;
+    int kernel = 0, terms = s->mt, flags = 0, threads = 256, width = 0, fm = 0, panels = 1;
+    bool tile = false;
+    if (op == NEP_PLAN_K1) {
+        switch (k1_choice(s, k)) {
+            case K1_TILE: nep_tiles_plan(s->tiles, 0, k, 0, tp); tile = true; break;
+            case K1_FOLD: kernel = NEP_PLAN_K_SPMV_FOLD; flags = sell; width = sell ? 64 : s->lanes; break;
+            case K1_KFUSED: kernel = NEP_PLAN_K_SPMV_KFUSED; flags = sell; width = sell ? 64 : s->lanes; break;
+            default: kernel = NEP_PLAN_K_VC_SPMV; flags = sell; width = sell ? 64 : s->lanes; terms = std::min(s->mt, 4); fm = vc_rows(s); break;
+        }
+    } else if (op == NEP_PLAN_K2_CM) {
+        const int ch = k2_cm_choice(s, k);
+        if (ch == K2_NONE) { nep_set_error("column-major K2: no footprint tiles for this matrix / k"); return NEP_ERR_UNSUPPORTED; }
+        nep_tiles_plan(s->tiles, ch == K2_SP ? 2 : 3, k, 1, tp); tile = true;
+    } else {
+        const int32_t P = resid_panel_width(s->mt);
+        const int kk = std::min(P, k);
+        panels = (k + P - 1) / P;
+        const int ch = k2_choice(s, kk);
+        if (ch == K2_SPMM) {
+            const SpmmShape sh = spmm_shape(s, kk, k, 0, spmm_grid(s, op == NEP_PLAN_K2_NORMS));
+            kernel = sh.grouped ? NEP_PLAN_K_SPMM_RM_G : NEP_PLAN_K_SPMM_RM;
+            flags = sh.xcd_rows ? NEP_PLAN_F_XCD_ROWS : 0; width = sh.nch;
+        } else { nep_tiles_plan(s->tiles, ch == K2_SP ? 2 : 1, kk, 0, tp); tile = true; }
+    }
+    if (tile) { kernel = (int)tp[0]; terms = (int)tp[1]; flags = (int)tp[2] | sell; threads = (int)tp[3]; width = (int)tp[4]; fm = (int)tp[5]; }
+    info[0] = kernel; info[1] = s->valbytes; info[2] = terms; info[3] = flags; info[4] = threads; info[5] = width; info[6] = fm; info[7] = panels;
     return NEP_OK;
 }
 
@@ -1289,7 +1361,7 @@ int32_t nep_spmm_terms(nep_spmf* s, int32_t p, const nep_cdouble* dXT, int64_t l
     ARGCHK(s && dXT && dZT);
     ARGCHK(p >= 1 && p <= 256 && ldx >= (int64_t)p * s->mt && ldz >= p);
     hipStream_t st = as_stream(stream);
-    int grid = (int)std::min<int64_t>((s->n + 3) / 4, 4096);
+    int grid = spmm_grid(s, false);
     if (s->valbytes == 8)
         return launch_spmm<double>(s, p, nullptr, (const cplx*)dXT, ldx, p, (cplx*)dZT, ldz, nullptr, grid, st);
     return launch_spmm<cplx>(s, p, nullptr, (const cplx*)dXT, ldx, p, (cplx*)dZT, ldz, nullptr, grid, st);

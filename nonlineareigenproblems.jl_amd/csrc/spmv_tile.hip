@@ -1383,14 +1383,28 @@ void nep_tiles_info(const NepTiles* t, int64_t info[8]) {
     info[7] = t->nent * (2 + t->valbytes) + t->nfp * 4 + (int64_t)t->nblk * (int64_t)sizeof(TileDesc);
 }
 
+// entries streamed once from HBM (non-temporal loads) against re-read from L2 by every call (small matrices)
+static bool tile_large(const NepTiles* t) { return t->n >= 32768; }
 // threads per workgroup / split of the k columns over thread groups, by matrix size and k (see the kernel's header)
 static void tiles_launch_shape(const NepTiles* t, int k, int* nthr, int* split) {
     *nthr = 256; *split = 0;
-    if (t->n < 32768) {
+    if (!tile_large(t)) {
         static const int force = env_int("NEP_K1_TILE_THREADS", 0);
         *nthr = force ? force : (k >= 48 ? 1024 : (k >= 16 ? 512 : 256));
         *split = (k >= 4 && ((t->fcap + 15) & ~15) * 2 <= *nthr) ? 1 : 0;
     }
+}
+// the launch shapes below are decided in ONE function each, which the launcher and nep_tiles_plan (the dispatch query behind
+// nep_spmf_plan) both call
+struct TileK1Shape { int nthr, split, mtc; bool nt, pf; };
+static TileK1Shape tile_k1_shape(const NepTiles* t, int k) {
+    static const int pf_on = env_int("NEP_K1_TILE_PF", 1);
+    TileK1Shape s;
+    tiles_launch_shape(t, k, &s.nthr, &s.split);
+    s.nt = tile_large(t);
+    s.pf = s.nt && pf_on && t->rbmax <= 512;      // the register prefetch covers 2 x 256 rows per block (k_tile_mlincomb: rb <= 2 nthr)
+    s.mtc = std::min(t->mt, 4);
+    return s;
 }
 size_t nep_tiles_shmem(const NepTiles* t, int k) {
     int nthr, split; tiles_launch_shape(t, k, &nthr, &split);
@@ -1402,11 +1416,9 @@ int nep_tiles_mlincomb(const NepTiles* t, int k, const cplx* dC, int64_t ldc, co
     const size_t shm = nep_tiles_shmem(t, k);
     if (shm > 160 * 1024) { nep_set_error("tiled K1: k = %d needs %zu bytes of LDS", k, shm); return NEP_ERR_ARG; }
     static const int swz = env_int("NEP_XCD_SWIZZLE", 1);
-    static const int pf_on = env_int("NEP_K1_TILE_PF", 1);
-    int nthr, split; tiles_launch_shape(t, k, &nthr, &split);
-    const bool nt = t->n >= 32768;          // entries streamed once (HBM) vs re-read from L2 by every call (small matrices)
-    const bool pf = nt && pf_on && t->rbmax <= 512;      // the register prefetch covers 2 x 256 rows per block (k_tile_mlincomb: rb <= 2 nthr)
-    const int mtc = std::min(t->mt, 4);
+    const TileK1Shape sh = tile_k1_shape(t, k);
+    const int nthr = sh.nthr, split = sh.split, mtc = sh.mtc;
+    const bool nt = sh.nt, pf = sh.pf;
 #define TL(VT, M, NTF, PFF)                                                                                                    \
     do {                                                                                                                       \
         if (shm > 64 * 1024) {                                                                                                 \
@@ -1440,6 +1452,10 @@ bool nep_tiles_resid_ok(const NepTiles* t, int k) {
     return t->mt <= 4 && nep_tiles_resid_shmem(t, k, nep_tiles_resid_ps(t, k)) <= 160 * 1024;
 }
 
+static int tile_cm_ps() {
+    static const int ps_env = env_int("NEP_K2_CM_PS", 2);
+    return ps_env == 8 ? 8 : (ps_env == 4 ? 4 : 2);
+}
 // partial: [nblk][2][k] doubles (|r|^2 then |q|^2 per column), or NULL; ZT (n x k row-major, ld ldz) or NULL
 // column-major Q (n x k, ld ldq >= n) and, when given, column-major R: see k_tile_resid_cm
 int nep_tiles_resid_cm(const NepTiles* t, int k, const cplx* dF, const cplx* Q, int64_t ldq, cplx* R, int64_t ldr, double* partial,
@@ -1447,12 +1463,11 @@ int nep_tiles_resid_cm(const NepTiles* t, int k, const cplx* dF, const cplx* Q, 
     if (t->mt > 4) { nep_set_error("tiled K2 (column-major): mt = %d not supported", t->mt); return NEP_ERR_ARG; }
     // columns per panel: 2 (measured at n = 1e6, k = 60: 0.51 ms with 2, 0.64 with 4, 1.24 with 8 -- the smaller tile leaves
     // room for more workgroups per CU, and the kernel is bound by the dependent loads of each workgroup, not by bytes)
-    static const int ps_env = env_int("NEP_K2_CM_PS", 2);
-    const int ps = ps_env == 8 ? 8 : (ps_env == 4 ? 4 : 2);
+    const int ps = tile_cm_ps();
     const size_t shm = (size_t)t->fcap * ps * sizeof(cplx) + (size_t)2 * 4 * ps * sizeof(double);
     if (shm > 160 * 1024) { nep_set_error("tiled K2 (column-major): footprint too large"); return NEP_ERR_ARG; }
     static const int swz = env_int("NEP_XCD_SWIZZLE", 1);
-    const bool nt = t->n >= 32768;
+    const bool nt = tile_large(t);
     const int npan = (k + ps - 1) / ps;
     static const int order = env_int("NEP_K2_CM_ORDER", 1);      // 1: panels of a block back to back on one XCD (1-D launch); 0: panels as grid.y
     const dim3 grid = order ? dim3((unsigned)(8 * ((t->nblk + 7) / 8) * npan)) : dim3((unsigned)t->nblk, (unsigned)npan);
@@ -1495,14 +1510,30 @@ bool nep_tiles_resid_sp_ok(const NepTiles* t, int k, int cm) {
     if (t->fcap > fpad || SP_PSW * (fpad / 64) > SP_IMAX * (nthr / 64)) return false;          // tile pitch; DMA instructions per wave
     return sp_shmem(t, nthr) + (size_t)fpad * 4 <= 160 * 1024;
 }
+// persistent form and ring of four (see the measurements in nep_tiles_resid_sp), flush mask of the slot layout
+struct TileSpShape { int nthr, fm; bool pers, ring4; };
+static TileSpShape tile_sp_shape(const NepTiles* t, int k, int cm) {
+    static const int persist = env_int("NEP_K2_SP_PERSIST", 0);
+    TileSpShape s;
+    s.nthr = sp_threads(t);
+    // NEP_K2_SP_PERSIST = 0 (default) never, 1 for 4 < k <= 12, 2 always (k > 4)
+    s.pers = k > SP_PSW && (persist == 2 || (persist == 1 && k <= 3 * SP_PSW));
+    s.ring4 = cm && !s.pers && env_int("NEP_K2_SP_RING", 2) == 4;
+    // bit j = slot j is the last of its term; the kernels exist for one term (0x80), the 5 + 2 + 1 layout (0xD0) and flushing
+    // after every slot (0xFF), which is right for any layout
+    int fm = 0x80;
+    for (int j = 0; j < 7; ++j) if (((t->slot_terms >> (4 * j)) & 15u) != ((t->slot_terms >> (4 * (j + 1))) & 15u)) fm |= 1 << j;
+    s.fm = (fm == 0xD0 || fm == 0x80) ? fm : 0xFF;
+    return s;
+}
 int nep_tiles_resid_sp(const NepTiles* t, int k, const cplx* dF, const cplx* Q, int64_t ldq, int cm, cplx* R, int64_t ldr,
                        double* partial, int64_t split_row, hipStream_t st) {
     if (!nep_tiles_resid_sp_ok(t, k, cm)) { nep_set_error("super-panel K2: not available for this matrix / k = %d / layout %d", k, cm); return NEP_ERR_ARG; }
-    const int nthr = sp_threads(t);
+    const TileSpShape sh = tile_sp_shape(t, k, cm);
+    const int nthr = sh.nthr;
     const size_t shm = sp_shmem(t, nthr) + (size_t)SP_FPAD(nthr) * 4;          // (+ the second footprint list of the persistent form)
     static const int swz = env_int("NEP_XCD_SWIZZLE", 1);
     // persistent form (k_tile_resid_spp) from two panels on: one workgroup per CU (the tiles leave room for one), a multiple of 8
-    static const int persist = env_int("NEP_K2_SP_PERSIST", 0);
     static int ncu = 0;
     if (!ncu) {
         int dev = 0; hipDeviceProp_t pr;
@@ -1516,18 +1547,16 @@ int nep_tiles_resid_sp(const NepTiles* t, int k, const cplx* dF, const cplx* Q, 
     // entries the persistent form sits at the 168-VGPR budget of a 768-thread workgroup and spills since the row-major tile layout
     // added its address arithmetic (84.7 against 70 us per launch at k = 8): OPT-IN.  NEP_K2_SP_PERSIST = 0 (default) never,
     // 1 for 4 < k <= 12, 2 always (k > 4)
-    const bool pers = k > SP_PSW && (persist == 2 || (persist == 1 && k <= 3 * SP_PSW));
+    const bool pers = sh.pers;
     // column-major blocks: NEP_K2_SP_RING=4 selects the ring of four half-tiles (k_tile_resid_sp4).  MEASURED (round 6, n = 1e6,
     // k = 60): 0.361 ms against 0.311 ms of the two-tile kernel -- three half-panels in flight instead of one panel did not help,
     // twice as many barriers / wave reductions per block cost 0.3 us each: the kernel is NOT waiting for HBM latency (see DESIGN
     // section 7, round 6: the per-panel arithmetic + LDS time equals the panel's HBM time).  Opt-in, tested.
     // (also tried: RING = 2 with half the LDS so that TWO 768-thread workgroups share a CU -- 24 waves leave 80 VGPRs per lane, the
     // kernel needs 111: 36 spills, their scratch reloads drain the DMA queue inside the panel loop, 0.73 ms.  Not kept.)
-    const bool ring4 = cm && !pers && env_int("NEP_K2_SP_RING", 2) == 4;
+    const bool ring4 = sh.ring4;
     const int pgrid = std::min(ncu, (t->nblk + 7) / 8 * 8);
-    // flush mask of the slot layout: bit j = slot j is the last of its term
-    int fm = 0x80;
-    for (int j = 0; j < 7; ++j) if (((t->slot_terms >> (4 * j)) & 15u) != ((t->slot_terms >> (4 * (j + 1))) & 15u)) fm |= 1 << j;
+    const int fm = sh.fm;
 #define SPL(VT, C, NT_, FM_)                                                                                                   \
     do {                                                                                                                       \
         if (pers) {                                                                                                            \
@@ -1573,7 +1602,7 @@ int nep_tiles_resid(const NepTiles* t, int k, const cplx* dF, const cplx* QT, in
     const size_t shm = nep_tiles_resid_shmem(t, k, ps);
     if (t->mt > 4 || shm > 160 * 1024) { nep_set_error("tiled K2: mt = %d, k = %d not supported", t->mt, k); return NEP_ERR_ARG; }
     static const int swz = env_int("NEP_XCD_SWIZZLE", 1);
-    const bool nt = t->n >= 32768;
+    const bool nt = tile_large(t);
 #define RL(VT, M, P, NTF)                                                                                                      \
     do {                                                                                                                       \
         if (shm > 64 * 1024) {                                                                                                 \
@@ -1592,6 +1621,29 @@ int nep_tiles_resid(const NepTiles* t, int k, const cplx* dF, const cplx* QT, in
 #undef RL
     LAUNCHCHK();
     return NEP_OK;
+}
+
+// what the launchers above would start for k columns: op 0 = K1 (nep_tiles_mlincomb), 1 = row-major K2 (nep_tiles_resid),
+// 2 = super-panel K2 (nep_tiles_resid_sp, cm = layout), 3 = column-major K2 (nep_tiles_resid_cm).  p[0] = kernel (NEP_PLAN_K_*),
+// p[1] = terms unrolled, p[2] = flags, p[3] = threads, p[4] = panel width, p[5] = flush mask.  Launches nothing.
+void nep_tiles_plan(const NepTiles* t, int op, int k, int cm, int64_t p[6]) {
+    for (int i = 0; i < 6; ++i) p[i] = 0;
+    if (op == 0) {
+        const TileK1Shape s = tile_k1_shape(t, k);
+        p[0] = NEP_PLAN_K_TILE_MLINCOMB; p[1] = s.mtc; p[3] = s.nthr;
+        p[2] = (s.nt ? NEP_PLAN_F_NT : 0) | (s.pf ? NEP_PLAN_F_PREFETCH : 0) | (s.split ? NEP_PLAN_F_COLSPLIT : 0);
+    } else if (op == 1) {
+        p[0] = NEP_PLAN_K_TILE_RESID; p[1] = std::min(t->mt, 4); p[3] = 256; p[4] = nep_tiles_resid_ps(t, k);
+        p[2] = tile_large(t) ? NEP_PLAN_F_NT : 0;
+    } else if (op == 2) {
+        const TileSpShape s = tile_sp_shape(t, k, cm);
+        p[0] = s.pers ? NEP_PLAN_K_TILE_RESID_SPP : (s.ring4 ? NEP_PLAN_K_TILE_RESID_SP4 : NEP_PLAN_K_TILE_RESID_SP);
+        p[1] = t->mt; p[3] = s.nthr; p[4] = SP_PSW; p[5] = s.fm;
+        p[2] = (s.pers ? NEP_PLAN_F_PERSISTENT : 0) | (s.ring4 ? NEP_PLAN_F_RING : 0);
+    } else {
+        p[0] = NEP_PLAN_K_TILE_RESID_CM; p[1] = std::min(t->mt, 4); p[3] = 256; p[4] = tile_cm_ps();
+        p[2] = tile_large(t) ? NEP_PLAN_F_NT : 0;
+    }
 }
 
 }  // extern "C"
