@@ -578,8 +578,8 @@ int32_t nep_lu_refac_info(const nep_lu_refac* r, int64_t out[6]);
  * [4] = deferred products (updates into a panel's own later rows / columns, applied at the end of the level). */
 int32_t nep_lu_refac_wide_info(const nep_lu_refac* r, int64_t out[5]);
 /* out[0] = hash of the plan arrays as they sit on the device (the quantity nep_lu_refac_analyze returns in out[7] for the host
- * enumeration of the same inputs), out[1] = 1 when the products were enumerated on the device (default; NEP_LU_PLAN_GPU=0: on
- * host threads).  Round 3: the enumeration of nep_lu_refac_create runs on the GPU (0.10-0.18 s -> a few ms for the gun pattern). */
+ * enumeration of the same inputs), out[1] = 1 when the products were enumerated on the device (the default), 0 when on
+ * host threads (the fallback).  Round 3: the enumeration of nep_lu_refac_create runs on the GPU (0.10-0.18 s -> a few ms for the gun pattern). */
 int32_t nep_lu_refac_hash(const nep_lu_refac* r, int64_t out[2]);
 int32_t nep_lu_factor_dev(nep_lu_refac* r, const nep_cdouble* h_Ax, int32_t expected_solves, double growth_limit,
                           double* h_health, nep_cdouble* h_LUx_out, nep_lu** out, nep_stream stream);

@@ -7,6 +7,8 @@ restricts every thread of the process to the GPU-local CPUs (read from sysfs); i
 and NEP_NO_PIN=1 disables it."""
 import os
 
+from ._env import env_flag
+
 _done = {}
 
 
@@ -37,7 +39,7 @@ def gpu_local_cpus(device_index=0):
 
 def pin_to_gpu_numa(device_index=0):
     """returns the CPU set the process was restricted to (None if nothing was changed)"""
-    if os.environ.get("NEP_NO_PIN") or not hasattr(os, "sched_setaffinity"):
+    if env_flag("NEP_NO_PIN") or not hasattr(os, "sched_setaffinity"):
         return None
     if device_index in _done:
         return _done[device_index]

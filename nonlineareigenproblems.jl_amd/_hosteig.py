@@ -6,7 +6,6 @@ that feeds the GPU.  ctypes releases the GIL, so zgeev is called directly in the
 SciPy already loaded (found through threadpoolctl).  Falls back to numpy.linalg.eig when the symbol is unavailable.
 Same LAPACK routine, same output convention (right eigenvectors, unit 2-norm) as `eigen` in the reference."""
 import ctypes as C
-import os as _os
 
 import numpy as np
 
@@ -89,7 +88,7 @@ def eig(H, hessenberg=False):
     n = H.shape[0]
     if f is None or n == 0:
         return np.linalg.eig(H)
-    if hessenberg and n >= 48 and _HESS[0] and not _os.environ.get("NEP_EIG_ZGEEV"):
+    if hessenberg and n >= 48 and _HESS[0]:
         r = _eig_hessenberg(H, n)
         if r is not None:
             return r

@@ -8,6 +8,8 @@ import os
 import numpy as np
 import torch  # noqa: F401  (loads the HIP runtime that the library binds to -- see build.py)
 
+from ._env import env_flag
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libnepmi355.so")
 
@@ -32,7 +34,7 @@ def _load():
             build.build_lib(verbose=False)        # serialised across processes by a file lock, linked to a temp name + rename
         elif not os.path.exists(LIB_PATH):
             raise ImportError("libnepmi355.so is missing and hipcc is not available to build it")
-        elif not os.environ.get("NEP_ALLOW_STALE_LIB"):
+        elif not env_flag("NEP_ALLOW_STALE_LIB"):
             raise ImportError("libnepmi355.so was built from other sources than the ones in %s (digest %s, sources %s) and hipcc "
                               "is not available to rebuild it; NEP_ALLOW_STALE_LIB=1 loads it anyway"
                               % (build.CSRC, build.built_digest(), build.source_digest()))
@@ -43,7 +45,7 @@ def _load():
         have = l.nep_src_digest().decode()
     except AttributeError:
         have = None
-    if have != build.source_digest() and not os.environ.get("NEP_ALLOW_STALE_LIB"):
+    if have != build.source_digest() and not env_flag("NEP_ALLOW_STALE_LIB"):
         raise ImportError("libnepmi355.so reports source digest %r, the binding expects %r" % (have, build.source_digest()))
     return l
 

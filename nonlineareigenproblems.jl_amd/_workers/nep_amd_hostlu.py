@@ -214,7 +214,7 @@ def factor(data, indices, indptr, shape, permc_spec=None, diag_pivot_thresh=None
     # kept per pattern (the 64 nodes of a contour, the factorisations of nleigs, repeated solves of one problem) and the
     # next matrix with that pattern is handed to SuperLU already permuted with permc_spec = "NATURAL": identical pivots and
     # factors, without the ordering pass (gun: 16 -> 13 ms per factorisation).
-    order = _cached_order(Ac, permc_spec, bool(symmetric_mode)) if not os.environ.get("NEP_NO_ORDER_CACHE") else None
+    order = _cached_order(Ac, permc_spec, bool(symmetric_mode))
     with _blas_limit(nthreads):
         if order is None:
             lu = spla.splu(Ac, **kw)  # RuntimeError("Factor is exactly singular") propagates to the caller

@@ -12,7 +12,6 @@ sums stay on the device (K8 = nep_axpy).  `MatrixTrapezoidalSharded` gives rank 
 i = r (mod P); the only exchange is ONE all-gather of the 2 n k partial block, followed by a
 fixed-order sum so that every rank holds bit-identical A0, A1.
 """
-import os
 
 import numpy as np
 import scipy.linalg as sla
@@ -20,6 +19,7 @@ import torch
 import torch.distributed as dist
 
 from . import dense
+from ._env import env_flag, env_str
 from .errmeasure import DefaultErrmeasure, estimate_errors
 from .linsolvers import BackslashLinSolverCreator, DeviceLU, HostLUPool, create_linsolver, lin_solve, _DeviceRefactor
 from .nep import CDT, to_dev, to_host
@@ -88,8 +88,8 @@ def integrate_interval(ST, f, gv, a, b, N, info=None, ops=_DeviceOps):
     # Node solves whose factors are all on the device already (the batched numeric LU): the solve of one node is a chain of ~15 kernels
     # that do not fill the chip (32 right-hand sides, 0.64 ms per node on gun), and the nodes are independent -- they go round robin
     # onto two side streams, each result into its own block, and are accumulated on the caller's stream IN NODE ORDER (the sum
-    # is the same, to the bit, as with one stream).  NEP_BEYN_SOLVE_STREAMS=1: one stream as before.
-    nstreams = int(os.environ.get("NEP_BEYN_SOLVE_STREAMS", "2"))    # measured on C4: 83.0 / 76.9 / 78-110 / 80.2 / 79.2 ms with 1 / 2 / 3 / 4 / 8 streams
+    # is the same, to the bit, as with one stream).
+    nstreams = 2    # measured on C4: 83.0 / 76.9 / 78-110 / 80.2 / 79.2 ms with 1 / 2 / 3 / 4 / 8 streams
     ready = getattr(f, "ready", None)
     if nstreams > 1 and ready and torch.cuda.is_available() and all(t[i] in ready for i in mine) and len(mine) > 1:
         cur = torch.cuda.current_stream()
@@ -154,8 +154,8 @@ class _NodeSolve:
     node needs a NEW host factorisation; `prefetch` starts all factorisations of this rank's nodes in worker processes
     so that they run concurrently with each other and with the device solves of the nodes already factored."""
 
-    BUILDERS = int(os.environ.get("NEP_BEYN_BUILDERS", "4"))   # threads turning host factors into device schedules (nep_lu_create releases the GIL)
-    AHEAD = int(os.environ.get("NEP_BEYN_AHEAD", "8"))         # device factorisations built (or being built) ahead of the node being solved
+    BUILDERS = 4   # threads turning host factors into device schedules (nep_lu_create releases the GIL)
+    AHEAD = 8      # device factorisations built (or being built) ahead of the node being solved
 
     def __init__(self, nep, linsolvercreator, sigma, g, Vd, weight):
         self.nep, self.creator, self.sigma, self.g, self.Vd, self.weight = nep, linsolvercreator, sigma, g, Vd, weight
@@ -195,7 +195,7 @@ class _NodeSolve:
         from concurrent.futures import ThreadPoolExecutor
         self.pool = ThreadPoolExecutor(max_workers=self.BUILDERS)
         self.order = list(ts)
-        trace = os.environ.get("NEP_BEYN_TRACE")
+        trace = env_flag("NEP_BEYN_TRACE")
         if trace:
             import time as _t
             self._t0 = _t.perf_counter(); self._host_done = []; self._host_meta = []
@@ -205,7 +205,7 @@ class _NodeSolve:
         self.ready = {}
         ts_host = list(ts)
         if (_DeviceRefactor.enabled() and hasattr(self.nep, "aligned_terms_dev") and c.permc_spec is None and not c.lu_kw
-                and not os.environ.get("NEP_BEYN_HOST_LU")):
+                and not env_flag("NEP_BEYN_HOST_LU")):
             al = self.nep.aligned_terms_dev()
             if al is not None:
                 indptr, indices, D_dev, G = al
@@ -215,7 +215,7 @@ class _NodeSolve:
                 A0 = _Pattern(); A0.indptr = indptr; A0.indices = indices; A0.shape = (self.nep.n, self.nep.n)
                 plan = _DeviceRefactor.lookup(_DeviceRefactor.key(A0, (None, None, None)))
                 lu_first = None
-                if plan is None and len(ts) >= 4 and os.environ.get("NEP_BEYN_COLD_PLAN", "1") != "0":
+                if plan is None and len(ts) >= 4 and env_str("NEP_BEYN_COLD_PLAN", "1") != "0":
                     # FIRST call on this sparsity pattern: instead of sending all N nodes to the host-factorisation worker pool (gun,
                     # N = 64: 0.67 s for the call, most of it the pool's start-up and 64 SuperLU runs) the first node is factorised on
                     # the host in this process, its device-LU plan is built right away (enumeration on the GPU, ~25 ms) and waited
@@ -312,7 +312,7 @@ class _NodeSolve:
                 self.close()
                 raise
             if not self.built and self.next >= len(self.order):
-                if os.environ.get("NEP_BEYN_TRACE"):
+                if env_flag("NEP_BEYN_TRACE"):
                     import time as _t
                     hd = sorted(self._host_done)
                     mt_ = [m_ for m_ in self._host_meta if "t_worker" in m_]
@@ -417,7 +417,7 @@ def contour_beyn(nep, MIntegrator=MatrixTrapezoidal, tol=np.sqrt(EPS), sigma=0.0
 
     S = integrate_interval(MIntegrator, f, [lambda s: 1.0 + 0j, g], 0.0, 2 * np.pi, N, info=info)
     tp = _time.perf_counter()
-    dev_tail = (S.is_cuda and k >= 2 and os.environ.get("NEP_BEYN_DEVICE_TAIL", "1") != "0")
+    dev_tail = (S.is_cuda and k >= 2 and env_str("NEP_BEYN_DEVICE_TAIL", "1") != "0")
     A0 = A1 = None
     lam = None
     if dev_tail:

@@ -112,6 +112,12 @@ __device__ __forceinline__ double readlane_d(double v, int lane) {
 
 static inline hipStream_t as_stream(nep_stream s) { return (hipStream_t)s; }
 
+// ---- environment switches (DESIGN.md section 6 lists every one) ----------------------------------------------------------
+// Read on every call: a site that wants the value once per process keeps its own `static const`.
+static inline int nep_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static inline double nep_env_double(const char* name, double dflt) { const char* e = getenv(name); return e ? atof(e) : dflt; }
+static inline bool nep_env_flag(const char* name) { const char* e = getenv(name); return e && atoi(e) != 0; }   // set AND non-zero
+
 // stacked-CSR index packing: high 7 bits = term (<= 128 terms: the particle example of test/nleigs has 83),
 // low 25 bits = column (n <= 33.5 M)
 #define NEP_TERM_SHIFT 25
@@ -165,15 +171,11 @@ int nep_mlincomb_dev_shift(nep_spmf* s, int32_t k, const nep_cdouble* dC, int64_
 int32_t nep_orth_dev_mirror(const nep_cdouble* dV, int64_t ldv, int64_t rows, int32_t k, const int64_t* d_active_rows,
                             nep_cdouble* dw, nep_cdouble* d_out, int32_t method, nep_cdouble* d_mirror, int32_t nmirror,
                             nep_stream stream);
-// ... and with an event (hipEvent_t or NULL) the stream waits for before the first kernel that writes w
-int32_t nep_orth_dev_mirror_ev(const nep_cdouble* dV, int64_t ldv, int64_t rows, int32_t k, const int64_t* d_active_rows,
-                               nep_cdouble* dw, nep_cdouble* d_out, int32_t method, nep_cdouble* d_mirror, int32_t nmirror,
-                               void* before_write, nep_stream stream);
 // orth.hip: iar's form (rows = n (k + 1)): the last kernel also forms step k + 1's coefficient product d_WT (n x mt) from the
 // normalised vector and writes its block shift to d_shift (k_orth_finish_vc); spmv.hip: the SpMV on such a product
 int32_t nep_orth_dev_iar_next(const nep_cdouble* dV, int64_t ldv, int64_t n, int32_t k, const int64_t* d_active_rows,
                               nep_cdouble* dw, nep_cdouble* d_out, int32_t method, nep_cdouble* d_mirror, int32_t nmirror,
-                              void* before_write, const nep_cdouble* dC, int64_t ldc, int32_t mt, nep_cdouble* d_WT,
+                              const nep_cdouble* dC, int64_t ldc, int32_t mt, nep_cdouble* d_WT,
                               nep_cdouble* d_shift, nep_stream stream);
 int nep_spmv_wt(nep_spmf* s, const nep_cdouble* d_WT, nep_cdouble* dz, hipStream_t st);
 }

@@ -30,9 +30,6 @@ struct nep_iar {
     cplx* hH_dev;                            // device address of the pinned block (NULL: not mapped, rows travel by memcpy)
     int32_t method;
     std::vector<hipEvent_t> ev;              // ev[k]: H column k is in pinned memory
-    // the recorded residual of the kept iterate (a pure check: nothing of the recurrence depends on it) runs on a side stream
-    // next to the projections of the Gram-Schmidt pass; the pass' first write to the vector waits for it
-    hipStream_t side = nullptr; hipEvent_t e_solved = nullptr, e_checked = nullptr;
     hipEvent_t e_upload = nullptr; bool upload_waited = false;      // |f_t|, f_t were uploaded on the NULL stream
     hipStream_t last = nullptr;
     bool no_events = false;                  // nep_iar_steps_graph: the steps are being captured, their events are recorded behind the graph launch
@@ -70,28 +67,17 @@ int32_t nep_iar_create(nep_spmf* spmf, nep_lu* lu, int64_t n, int32_t m, nep_cdo
         // the steps run on the caller's stream, which need not be ordered behind the NULL stream (non-blocking streams)
         if (hipEventCreateWithFlags(&s->e_upload, hipEventDisableTiming) == hipSuccess) (void)hipEventRecord(s->e_upload, nullptr);
         else (void)hipGetLastError();
-        // MEASURED: slower (gun iar 45.1 ms per call against 42.8 ms): the two cross-stream dependencies per step cost more on
-        // the device than the 11 us kernel they take off the critical path.  Opt-in (NEP_IAR_RESID_OVERLAP=1).
-        static const int overlap = getenv("NEP_IAR_RESID_OVERLAP") ? atoi(getenv("NEP_IAR_RESID_OVERLAP")) : 0;
-        if (overlap && hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking) == hipSuccess) {
-            if (hipEventCreateWithFlags(&s->e_solved, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&s->e_checked, hipEventDisableTiming) != hipSuccess) {
-                (void)hipGetLastError(); (void)hipStreamDestroy(s->side); s->side = nullptr;
-            }
-        } else (void)hipGetLastError();
     }
     s->dH = (cplx*)dH; s->hH = h_pinnedH; s->method = orth_method;
-    const int fuse_vc = getenv("NEP_IAR_FUSE_VC") ? atoi(getenv("NEP_IAR_FUSE_VC")) : 1;      // (read per object: tests compare both forms)
+    const int fuse_vc = nep_env_int("NEP_IAR_FUSE_VC", 1);      // (read per object: tests compare both forms)
     if (fuse_vc && mt <= 4) {
         void* p = nullptr;
         if (nep_pool_alloc(&p, (size_t)n * mt * sizeof(cplx)) == 0) s->dWT = (cplx*)p;
     }
     s->ev.assign(m + 1, nullptr);
-    s->hH_dev = nullptr;
-    if (!getenv("NEP_IAR_NO_MIRROR")) {
-        void* dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, h_pinnedH, 0) == hipSuccess) s->hH_dev = (cplx*)dp; else (void)hipGetLastError();
-    }
+    s->hH_dev = nullptr;                      // (not mapped: the H rows travel by copy command)
+    void* dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, h_pinnedH, 0) == hipSuccess) s->hH_dev = (cplx*)dp; else (void)hipGetLastError();
     *out = s;
     return NEP_OK;
 }
@@ -103,9 +89,6 @@ int32_t nep_iar_destroy(nep_iar* s) {
         if (s->last) (void)hipStreamSynchronize(s->last);          // a graph must not be destroyed while it executes
         for (hipGraphExec_t g : s->graphs) (void)hipGraphExecDestroy(g);
     }
-    if (s->side) { (void)hipStreamSynchronize(s->side); (void)hipStreamDestroy(s->side); }
-    if (s->e_solved) (void)hipEventDestroy(s->e_solved);
-    if (s->e_checked) (void)hipEventDestroy(s->e_checked);
     if (s->e_upload) (void)hipEventDestroy(s->e_upload);
     // steps (speculative ones past convergence included) may still be queued on the last stream: the block goes back to the
     // pool behind them
@@ -159,18 +142,13 @@ int32_t nep_iar_step(nep_iar* s, int32_t k, int32_t refine_steps, nep_stream str
         }
         if (rc) return rc;
     }
-    void* before_write = nullptr;
-    if (record && !skip_final) {       // omega of the iterate that is kept (stored negated in vv)
-        hipStream_t cs = st;
-        if (s->side) {  // reads vv, z; writes dW and the omega word of this row: ordered behind the solve, ahead of the first update
-            HIPCHK(hipEventRecord(s->e_solved, st));
-            HIPCHK(hipStreamWaitEvent(s->side, s->e_solved, 0));
-            cs = s->side;
-        }
+    // omega of the iterate that is kept (stored negated in vv): a pure check, on the recurrence's own stream.  (On a side stream
+    // next to the Gram-Schmidt projections it was MEASURED slower, gun iar 45.1 ms per call against 42.8 ms: the two cross-stream
+    // dependencies per step cost more on the device than the 11 us kernel they take off the critical path.)
+    if (record && !skip_final) {
         rc = nep_cw_resid_dev(s->spmf, s->d_cabs, (const nep_cdouble*)s->d_ccf, (const nep_cdouble*)vv, (const nep_cdouble*)s->dz,
-                              (nep_cdouble*)s->dW, bits + refine_steps, -1.0, cs);
+                              (nep_cdouble*)s->dW, bits + refine_steps, -1.0, st);
         if (rc) return rc;
-        if (s->side) { HIPCHK(hipEventRecord(s->e_checked, s->side)); before_write = (void*)s->e_checked; }
     }
     if (!shifted) {
         rc = nep_iar_shift_scale(n, k, (const nep_cdouble*)col, (nep_cdouble*)vv, stream);
@@ -179,12 +157,12 @@ int32_t nep_iar_step(nep_iar* s, int32_t k, int32_t refine_steps, nep_stream str
     cplx* mirror = s->hH_dev ? s->hH_dev + (int64_t)(k - 1) * (s->m + 4) : nullptr;
     if (s->dWT && k < s->m) {           // + step k + 1's coefficient product and block shift (column k + 1, blocks 1 ..)
         rc = nep_orth_dev_iar_next((const nep_cdouble*)s->dV, s->ldv, n, k, s->d_active, (nep_cdouble*)vv, (nep_cdouble*)hrow, s->method,
-                                   (nep_cdouble*)mirror, k + 4, before_write, (const nep_cdouble*)s->dCtab, s->ldc, s->mt,
+                                   (nep_cdouble*)mirror, k + 4, (const nep_cdouble*)s->dCtab, s->ldc, s->mt,
                                    (nep_cdouble*)s->dWT, (nep_cdouble*)(vv + s->ldv + n), stream);
         if (!rc) s->wt_for = k + 1;
     } else
-        rc = nep_orth_dev_mirror_ev((const nep_cdouble*)s->dV, s->ldv, n * (int64_t)(k + 1), k, s->d_active, (nep_cdouble*)vv,
-                                    (nep_cdouble*)hrow, s->method, (nep_cdouble*)mirror, k + 4, before_write, stream);
+        rc = nep_orth_dev_mirror((const nep_cdouble*)s->dV, s->ldv, n * (int64_t)(k + 1), k, s->d_active, (nep_cdouble*)vv,
+                                 (nep_cdouble*)hrow, s->method, (nep_cdouble*)mirror, k + 4, stream);
     if (rc) return rc;
     if (!mirror)
         HIPCHK(hipMemcpyAsync(s->hH + (int64_t)(k - 1) * (s->m + 4), hrow, (size_t)(k + 4) * sizeof(cplx), hipMemcpyDeviceToHost, st));
@@ -249,24 +227,18 @@ int32_t nep_iar_steps_graph(nep_iar* s, int32_t k0, int32_t count, int32_t refin
 // blocks the calling thread until column k of H has reached the pinned buffer
 int32_t nep_iar_wait(nep_iar* s, int32_t k) {
     ARGCHK(s && k >= 1 && k <= s->m && s->ev[k]);
-    // NEP_IAR_POLL_LAST: 2 (default) = every waiter polls, 1 = only those of the last 13 steps, 0 = all sleep on the interrupt
-    static const int poll_last = getenv("NEP_IAR_POLL_LAST") ? atoi(getenv("NEP_IAR_POLL_LAST")) : 2;
-    if (poll_last == 2 || (poll_last && k > s->m - 13)) {
-        // the waiters poll (20 us naps) instead of sleeping on the event's interrupt: an interrupt-driven wait on this stack now
-        // and then wakes 20-35 ms late (seen as "wait eig" tails and as 20-35 ms hipDeviceSynchronize calls on an idle device,
-        // scripts/diag/tail_kernels.py) -- the checks are consumed in order, so a late waiter near the end delays the call --
-        // and the naps cost LESS CPU than the runtime's own wait (0.19 s instead of 0.43 s of CPU per headline call: at most
-        // LAG + 1 waiters exist at any time)
-        for (;;) {
-            const hipError_t e = hipEventQuery(s->ev[k]);
-            if (e == hipSuccess) return NEP_OK;
-            if (e != hipErrorNotReady) HIPCHK(e);
-            struct timespec ts = {0, 20000};
-            nanosleep(&ts, nullptr);
-        }
+    // the waiters poll (20 us naps) instead of sleeping on the event's interrupt: an interrupt-driven wait on this stack now
+    // and then wakes 20-35 ms late (seen as "wait eig" tails and as 20-35 ms hipDeviceSynchronize calls on an idle device,
+    // scripts/diag/tail_kernels.py) -- the checks are consumed in order, so a late waiter near the end delays the call --
+    // and the naps cost LESS CPU than the runtime's own wait (0.19 s instead of 0.43 s of CPU per headline call: at most
+    // LAG + 1 waiters exist at any time)
+    for (;;) {
+        const hipError_t e = hipEventQuery(s->ev[k]);
+        if (e == hipSuccess) return NEP_OK;
+        if (e != hipErrorNotReady) HIPCHK(e);
+        struct timespec ts = {0, 20000};
+        nanosleep(&ts, nullptr);
     }
-    HIPCHK(hipEventSynchronize(s->ev[k]));
-    return NEP_OK;
 }
 
 // orders `stream` behind step k without involving the host

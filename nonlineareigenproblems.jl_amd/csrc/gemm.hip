@@ -265,10 +265,9 @@ template <int NT>
 static int gemm_launch(bool rowmajor, const cplx* Z, int64_t ldz, int64_t rows, int k, const double* dB, int nks,
                        int p, int j0, cplx* Y, int64_t ldy, hipStream_t st) {
     // B-resident persistent kernel: all fragments in LDS (<= 144 KiB), tall blocks only (>= 16 strips per wave)
-    static const int res_mode = getenv("NEP_GEMM_RES") ? atoi(getenv("NEP_GEMM_RES")) : 1;
     const size_t res_bytes = (size_t)nks * NT * 2 * 64 * sizeof(double);
     // (NT = 8 with more than 16 k-steps would spill: 96 buffer + 64 accumulator registers)
-    if constexpr (NT <= 8) if (res_mode && nks <= (NT == 8 ? 16 : GEMM_RES_MAXKS) && res_bytes <= 147456 && rows >= GEMM_TALL_ROWS) {
+    if constexpr (NT <= 8) if (nks <= (NT == 8 ? 16 : GEMM_RES_MAXKS) && res_bytes <= 147456 && rows >= GEMM_TALL_ROWS) {
         static thread_local int ncu = 0;
         if (!ncu) { hipDeviceProp_t pr; int dev = 0; (void)hipGetDevice(&dev); ncu = (hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256; }
         const dim3 grid((unsigned)ncu), block(512);

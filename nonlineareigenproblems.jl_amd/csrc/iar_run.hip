@@ -73,11 +73,18 @@ struct RunStreams { hipStream_t check = nullptr, eig = nullptr; hipStream_t prob
 std::mutex g_rs_mu;
 std::map<int, RunStreams> g_rs;
 
-// first of up to `ncand` fresh streams (priority prio) that shares a hardware queue with none of `others` (probed, ~1.5 ms per
+// first of up to RUN_STREAM_CANDIDATES fresh streams that shares a hardware queue with none of `others` (probed, ~1.5 ms per
 // pair, once per process, device and caller stream); `keep` (may be NULL) is tried first.  The runtime maps streams onto a small
 // pool of hardware queues and gives no way to ask which: two streams on one queue serialise (measured: the convergence checks on
 // the recurrence's queue cost 15 ms per headline call).
-int pick_stream(hipStream_t keep, int prio, int ncand, bool probe, const std::vector<hipStream_t>& others, hipStream_t* out, bool* shared) {
+// Normal priority for both side streams.  MEASURED (round 6, 16 fresh processes): with a lowest-priority check stream half of the
+// processes ran the headline call in 57-69 ms instead of 32 -- both side streams then executed as if they shared the recurrence's
+// queue, although the probe had found them free; with normal priority 8 of 8 processes ran at 31.5-32.1 ms.  A highest-priority
+// decomposition stream (a decomposition is ONE workgroup that needs half a CU's LDS and has to find a CU between the recurrence's
+// kernels) stayed within 32.0-33.2 ms: no gain.
+constexpr int RUN_STREAM_CANDIDATES = 8;
+int pick_stream(hipStream_t keep, const std::vector<hipStream_t>& others, hipStream_t* out, bool* shared) {
+    const int prio = 0, ncand = RUN_STREAM_CANDIDATES;
     std::vector<hipStream_t> cand;
     if (keep) cand.push_back(keep);
     hipStream_t pick = nullptr;
@@ -86,7 +93,7 @@ int pick_stream(hipStream_t keep, int prio, int ncand, bool probe, const std::ve
         if ((size_t)c < cand.size()) s = cand[c];
         else { HIPCHK(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio)); cand.push_back(s); }
         bool clash = false;
-        for (size_t i = 0; probe && i < others.size() && !clash; ++i) {
+        for (size_t i = 0; i < others.size() && !clash; ++i) {
             int32_t a = 0;
             int rc = nep_stream_pair_serializes((nep_stream)others[i], (nep_stream)s, &a); if (rc) return rc;
             clash = a != 0;
@@ -108,22 +115,9 @@ int run_streams(hipStream_t main, RunStreams* out) {
     if (!r.check || !r.eig || r.probed_for != main || (r.shared && r.retries < 3)) {
         if (r.shared) ++r.retries;
         r.shared = false;
-        int least = 0, greatest = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        const int ncand = getenv("NEP_IAR_EIG_CANDIDATES") ? atoi(getenv("NEP_IAR_EIG_CANDIDATES")) : 8;
-        const bool probe = !(getenv("NEP_IAR_EIG_PROBE") && atoi(getenv("NEP_IAR_EIG_PROBE")) == 0);
-        // the convergence checks are off the critical path, but their stream gets NORMAL priority (NEP_IAR_CHECK_PRIO = 1: the device's
-        // lowest, -1: its highest).  MEASURED (round 6, 16 fresh processes): with a lowest-priority stream half of the processes ran
-        // the headline call in 57-69 ms instead of 32 -- both side streams then executed as if they shared the recurrence's queue,
-        // although the probe below had found them free; with normal priority 8 of 8 processes ran at 31.5-32.1 ms.  (The Python host's
-        // torch.cuda.Stream(priority=1) was clamped to normal by torch and never had a low-priority queue.)
-        const int cprio = getenv("NEP_IAR_CHECK_PRIO") ? (atoi(getenv("NEP_IAR_CHECK_PRIO")) > 0 ? least : (atoi(getenv("NEP_IAR_CHECK_PRIO")) < 0 ? greatest : 0)) : 0;
-        int rc = pick_stream(r.check, cprio, ncand, probe, {main}, &r.check, &r.shared); if (rc) return rc;
-        // the decompositions are 3 ms one-workgroup kernels next to both
-        // (NEP_IAR_EIG_PRIO: 0 = normal (default), -1 = the device's highest: a decomposition is ONE workgroup that needs half a CU's
-        // LDS and has to find a CU between the recurrence's kernels)
-        const int eprio = getenv("NEP_IAR_EIG_PRIO") ? (atoi(getenv("NEP_IAR_EIG_PRIO")) < 0 ? greatest : (atoi(getenv("NEP_IAR_EIG_PRIO")) > 0 ? least : 0)) : 0;
-        rc = pick_stream(r.eig, eprio, ncand, probe, {main, r.check}, &r.eig, &r.shared); if (rc) return rc;
+        // the convergence checks are off the critical path; the decompositions are 3 ms one-workgroup kernels next to both
+        int rc = pick_stream(r.check, {main}, &r.check, &r.shared); if (rc) return rc;
+        rc = pick_stream(r.eig, {main, r.check}, &r.eig, &r.shared); if (rc) return rc;
         r.probed_for = main;
     }
     *out = r;
@@ -329,10 +323,10 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
     const double t_entry = t_e_.tv_sec * 1e3 + t_e_.tv_nsec * 1e-6;
     const int32_t m = opts->maxit;
     if (m > 128) { nep_set_error("nep_iar_run: maxit = %d exceeds the device eigen-decomposition's limit 128", m); return NEP_ERR_UNSUPPORTED; }
-    const int BMAX = std::max(1, getenv("NEP_IAR_EIG_BATCH") ? atoi(getenv("NEP_IAR_EIG_BATCH")) : 16);
-    const int LASTB = std::max(1, getenv("NEP_IAR_EIG_LAST") ? atoi(getenv("NEP_IAR_EIG_LAST")) : 8);
-    const double T100 = getenv("NEP_IAR_EIG_MS100") ? atof(getenv("NEP_IAR_EIG_MS100")) : 3.3;
-    const double TSTEP = getenv("NEP_IAR_EIG_MSSTEP") ? atof(getenv("NEP_IAR_EIG_MSSTEP")) : 0.35;
+    const int BMAX = std::max(1, nep_env_int("NEP_IAR_EIG_BATCH", 16));
+    const int LASTB = std::max(1, nep_env_int("NEP_IAR_EIG_LAST", 8));
+    const double T100 = nep_env_double("NEP_IAR_EIG_MS100", 3.3);
+    const double TSTEP = 0.35;          // ms per Arnoldi step (gun, k ~ 100)
     const int cee = opts->check_error_every;
     const double neigs = opts->neigs;
     const bool unthrottled = isinf(neigs) && neigs > 0;
@@ -345,7 +339,7 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
     Arena& a = R.a;
     hipStream_t st = R.st, cst = R.rs.check, est = R.rs.eig;
     R.ref.umf = opts->umfpack_refinements > 0 ? opts->umfpack_refinements : 0;
-    R.ref.hint = (opts->refine_hint >= 0 && !(getenv("NEP_REFINE_HINT") && atoi(getenv("NEP_REFINE_HINT")) == 0)) ? opts->refine_hint : -1;
+    R.ref.hint = (opts->refine_hint >= 0 && nep_env_int("NEP_REFINE_HINT", 1) != 0) ? opts->refine_hint : -1;
     R.filled.assign(m + 1, 0); R.plans.assign(m + 1, 0);
     if (const char* fa = getenv("NEP_IAR_RUN_FAIL_AT")) { if (sscanf(fa, "%d:%d", &R.fail_kind, &R.fail_at) != 2) R.fail_kind = R.fail_at = 0; }
     if (h_err) for (int64_t i = 0; i < (int64_t)m * m; ++i) h_err[i] = NAN;
@@ -361,10 +355,10 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
     for (int64_t i = 0; i < n; ++i) { a.stage[i] = hc(h_v0[i]); nrm2 += h_v0[i].re * h_v0[i].re + h_v0[i].im * h_v0[i].im; }
     ARGCHK(nrm2 > 0.0 && isfinite(nrm2));
     HIPCHK(hipMemcpyAsync(a.v0, a.stage, (size_t)n * 16, hipMemcpyHostToDevice, st));
-    if (getenv("NEP_IAR_FULL_ZERO") && atoi(getenv("NEP_IAR_FULL_ZERO")))
+    if (nep_env_flag("NEP_IAR_FULL_ZERO"))
         HIPCHK(hipMemsetAsync(R.V, 0, (size_t)(m + 1) * R.ldv * 16, st));
     else {
-        if (getenv("NEP_IAR_POISON") && atoi(getenv("NEP_IAR_POISON"))) HIPCHK(hipMemsetAsync(R.V, 0xFF, (size_t)(m + 1) * R.ldv * 16, st));
+        if (nep_env_flag("NEP_IAR_POISON")) HIPCHK(hipMemsetAsync(R.V, 0xFF, (size_t)(m + 1) * R.ldv * 16, st));
         hipLaunchKernelGGL(k_iar_zero_slack, dim3((unsigned)(ZSLACK / 256), (unsigned)(m + 1)), dim3(256), 0, st, R.V, R.ldv, n, m + 1);
     }
     hipLaunchKernelGGL(k_iar_start, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, R.V, (const cplx*)a.v0, 1.0 / sqrt(nrm2), n);
@@ -401,10 +395,10 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
     double t_fv = 0;
     std::deque<int> pendA; std::deque<Batch> stA; std::deque<Check> stC;
     int slots = unthrottled ? m + 1 : std::max(BMAX, 4);
-    const int CHUNK = unthrottled ? (getenv("NEP_IAR_BATCH") ? std::max(1, atoi(getenv("NEP_IAR_BATCH"))) : 8) : 4;
+    const int CHUNK = unthrottled ? 8 : 4;          // steps per nep_iar_steps call
     const int P = std::min(256, std::max(1, 3072 / mt));        // panel width of nep_resid_batch_dev's output layout
     int k = 1; bool done = false; int status = NEP_OK;
-    const bool use_graph = getenv("NEP_IAR_GRAPH") && atoi(getenv("NEP_IAR_GRAPH")) != 0;
+    const bool use_graph = nep_env_flag("NEP_IAR_GRAPH");
     int n_graph = 0;
     auto finished = [&]() { return R.conv >= neigs; };
 
@@ -548,7 +542,7 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
                 }
                 if (nb > 0) {
                     int plan = R.ref.plan();
-                    if (plan > 0 && R.ref.settled() && !getenv("NEP_IAR_RECORD_ALL")) plan |= 0x100;
+                    if (plan > 0 && R.ref.settled()) plan |= 0x100;
                     // chunks after the first as hipGraphs (NEP_IAR_GRAPH, default off for the NULL stream: it cannot be captured)
                     if (use_graph && k > 1) { int32_t cap = 0; status = nep_iar_steps_graph(R.step, k, nb, plan, stream, &cap); n_graph += cap; }
                     else status = nep_iar_steps(R.step, k, nb, plan, stream);

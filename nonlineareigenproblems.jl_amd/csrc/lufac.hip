@@ -378,7 +378,7 @@ __global__ __launch_bounds__(512) void k_lu_int(int blk0, const int32_t* __restr
 // (pivot k by bisection of the product offsets, then (a, b) -> U entry a of row k and L entry b of column k, destination slot by
 // bisection of the union column), the positions of internal and wide products from ONE exclusive scan over the product
 // flags, the external products sorted by (destination segment, pivot) with a radix sort.  The arrays are bit-identical to the
-// host enumeration's (nep_lu_refac_hash against nep_lu_refac_analyze; NEP_LU_PLAN_GPU=0 keeps the host path).
+// host enumeration's (nep_lu_refac_hash against nep_lu_refac_analyze, which keeps the host enumeration).
 struct LuEnt { int32_t row; int32_t g; };
 struct LuEnumArgs {
     int64_t nprod; int32_t n;
@@ -696,7 +696,7 @@ int32_t nep_lu_refac_analyze(int64_t n, const int32_t* Lp, const int32_t* Li, co
 // the factor values do not depend on it.
 static int32_t refac_build_fused(nep_lu_refac* r, int64_t n, int64_t nF, int nlev, const int32_t* oldof, const int32_t* blk_se,
                                  const int32_t* lev_blk, const std::vector<int64_t>& cptr, const std::vector<Ent>& cent) {
-    const int P_env = getenv("NEP_LU_WIDE_P") ? atoi(getenv("NEP_LU_WIDE_P")) : 4;       // read per plan (tests build one per size)
+    const int P_env = nep_env_int("NEP_LU_WIDE_P", 4);       // read per plan (tests build one per size)
     const int P = std::max(1, std::min(LU_FUSE_MAXP, P_env));
     if (P < 2) return NEP_OK;
     (void)n;
@@ -903,8 +903,7 @@ static int32_t refac_build(nep_lu_refac* r, int64_t n, const int32_t* Lp, const 
     // with tens of thousands of products per pivot -- one workgroup cannot feed that (measured: 189 pivots 4.8 ms)
     r->wide.assign(nlev, 0);
     {
-        const char* e = getenv("NEP_LU_WIDE_MAXBLK");
-        const int maxblk = e ? atoi(e) : 16;      // gun: level 1 (10 blocks of up to 256 pivots) 2.5 ms in block mode, 1 ms wide
+        const int maxblk = 16;      // gun: level 1 (10 blocks of up to 256 pivots) 2.5 ms in block mode, 1 ms wide
         for (int l = 1; l < nlev; ++l) r->wide[l] = (lev_blk[l + 1] - lev_blk[l]) <= maxblk ? 1 : 0;
     }
     r->wstep0.assign(nlev + 1, 0);
@@ -982,8 +981,7 @@ static int32_t refac_build(nep_lu_refac* r, int64_t n, const int32_t* Lp, const 
     std::vector<std::vector<int32_t>> cnt_ext(nthr);
     std::vector<int32_t> tot;                                  // external products per destination slot
     // ---- the same on the device (see k_lu_enum_classify): host path when switched off, in the dry run, or when it fails
-    static const bool gpu_on = !(getenv("NEP_LU_PLAN_GPU") && atoi(getenv("NEP_LU_PLAN_GPU")) == 0);
-    bool gpu = gpu_on && !g_refac_dry && nF < ((int64_t)1 << LU_KIND_SHIFT);
+    bool gpu = !g_refac_dry && nF < ((int64_t)1 << LU_KIND_SHIFT);
     LuGpuEnum G;
     if (gpu) {
         G.pbase.assign(n + 1, 0); G.lstart.assign(n, 0); G.nL.assign(n, 0);
@@ -1319,9 +1317,8 @@ static int32_t lu_factor_batch_impl(nep_lu_refac* r, int32_t B, const nep_cdoubl
         accepted.push_back(b);
     }
     // the solve schedules of all accepted factors in one batched build (value gathers + block inverses with grid.y = factor);
-    // NEP_LU_BATCH_BUILD=0: one factor at a time as before
-    static const int batch_build = getenv("NEP_LU_BATCH_BUILD") ? atoi(getenv("NEP_LU_BATCH_BUILD")) : 1;
-    if (batch_build && accepted.size() > 1) {
+    // a single factor takes the plain build
+    if (accepted.size() > 1) {
         std::vector<const nep_cdouble*> pL(accepted.size()), pU(accepted.size());
         std::vector<MLFactor*> Fs(accepted.size(), nullptr);
         for (size_t a = 0; a < accepted.size(); ++a) {

@@ -489,7 +489,7 @@ static void launch_finish_vc(const OrthNextVc& nx, int kb, cplx* w, cplx* out_be
 // column groups per launch: enough workgroups to fill 256 CUs a few times over, otherwise as few as possible
 static int dots_grid_y(int nchunks, int k) {
     const int ngroups = (k + DOT_CG - 1) / DOT_CG;
-    static int target = getenv("NEP_DOTS_TARGET") ? atoi(getenv("NEP_DOTS_TARGET")) : 6144;   // measured 1024: 4.79, 4096: 5.17, 8192: 5.19, 16384: 5.09 TB/s
+    const int target = 6144;   // workgroups per launch; measured 1024: 4.79, 4096: 5.17, 8192: 5.19, 16384: 5.09 TB/s
     int gy = (target + nchunks - 1) / nchunks;
     return gy < 1 ? 1 : (gy > ngroups ? ngroups : gy);
 }
@@ -509,20 +509,19 @@ static thread_local NepScratch g_orth_scratch;
 // k = 8 at 10^6 rows: 62 / 67); inside the gun run, next to the eigenvalue kernels of the other queue, the row form is faster at
 // every k (whole call 37.7 ms against 39.3 with the switch at 64 and 39.7 without it), so it is the default for all k
 static int orth_rows_k() {
-    static const int v = getenv("NEP_ORTH_ROWS_K") ? atoi(getenv("NEP_ORTH_ROWS_K")) : 1 << 30;
+    static const int v = nep_env_int("NEP_ORTH_ROWS_K", 1 << 30);
     return v;
 }
 
 // non-temporal V loads when the streamed block is far larger than the last-level cache (see nep_orth_dev)
 static bool orth_use_nt(int64_t rows, int64_t k, bool staircase) {
-    static const int nt_env = getenv("NEP_ORTH_NT") ? atoi(getenv("NEP_ORTH_NT")) : -1;
-    static const double nt_mb = getenv("NEP_ORTH_NT_MB") ? atof(getenv("NEP_ORTH_NT_MB")) : 192.0;
+    const double nt_mb = 192.0;            // iar's staircase (see orth_dev_impl)
     // full columns (GMRES / tiar bases; no factorisation to protect next to them): the update's sweep over V follows the
     // projection's at once and finds a block of up to ~1.5x the last-level cache largely still there -- measured at 10^6 rows,
     // one pass: k = 12 103 -> 81 us, k = 16 114 -> 100, k = 20 146 -> 127, k = 24 158 -> 152 with ordinary loads
-    static const double nt_full_mb = getenv("NEP_ORTH_NT_FULL_MB") ? atof(getenv("NEP_ORTH_NT_FULL_MB")) : 512.0;
+    const double nt_full_mb = 512.0;
     const double streamed_mb = 16.0e-6 * (double)rows * (double)k * (staircase ? 0.5 : 1.0);
-    return nt_env >= 0 ? nt_env != 0 : streamed_mb > (staircase ? nt_mb : nt_full_mb);
+    return streamed_mb > (staircase ? nt_mb : nt_full_mb);
 }
 
 extern "C" int32_t nep_orth(const nep_cdouble* dV, int64_t ldv, int64_t rows, int32_t k,
@@ -631,7 +630,7 @@ extern "C" int32_t nep_orth(const nep_cdouble* dV, int64_t ldv, int64_t rows, in
 // held after the last enqueued pass.
 static int orth_dev_passes() {
     static int np = 0;
-    if (!np) { const char* e = getenv("NEP_ORTH_DEV_PASSES"); np = e ? atoi(e) : 2; if (np < 1 || np > 8) np = 2; }
+    if (!np) { np = nep_env_int("NEP_ORTH_DEV_PASSES", 2); if (np < 1 || np > 8) np = 2; }
     return np;
 }
 extern "C" int32_t nep_orth_dev(const nep_cdouble* dV, int64_t ldv, int64_t rows, int32_t k,
@@ -639,43 +638,35 @@ extern "C" int32_t nep_orth_dev(const nep_cdouble* dV, int64_t ldv, int64_t rows
                                 nep_stream stream) {
     return nep_orth_dev_mirror(dV, ldv, rows, k, d_active_rows, dw, d_out, method, nullptr, 0, stream);
 }
+static int orth_dev_impl(const nep_cdouble* dV, int64_t ldv, int64_t rows, int32_t k,
+                         const int64_t* d_active_rows, nep_cdouble* dw, nep_cdouble* d_out, int32_t method,
+                         nep_cdouble* d_mirror, int32_t nmirror, const OrthNextVc* next, nep_stream stream);
 // d_mirror / nmirror: see k_orth_finish (internal: nep_iar_step)
 extern "C" int32_t nep_orth_dev_mirror(const nep_cdouble* dV, int64_t ldv, int64_t rows, int32_t k,
                                        const int64_t* d_active_rows, nep_cdouble* dw, nep_cdouble* d_out, int32_t method,
                                        nep_cdouble* d_mirror, int32_t nmirror, nep_stream stream) {
-    return nep_orth_dev_mirror_ev(dV, ldv, rows, k, d_active_rows, dw, d_out, method, d_mirror, nmirror, nullptr, stream);
-}
-// before_write (may be NULL): an event the stream waits for before the first kernel that WRITES w (the first update): work on
-// another stream that still reads w -- iar's recorded residual of the kept iterate -- runs next to the projections
-static int orth_dev_impl(const nep_cdouble* dV, int64_t ldv, int64_t rows, int32_t k,
-                         const int64_t* d_active_rows, nep_cdouble* dw, nep_cdouble* d_out, int32_t method,
-                         nep_cdouble* d_mirror, int32_t nmirror, void* before_write, const OrthNextVc* next, nep_stream stream);
-extern "C" int32_t nep_orth_dev_mirror_ev(const nep_cdouble* dV, int64_t ldv, int64_t rows, int32_t k,
-                                          const int64_t* d_active_rows, nep_cdouble* dw, nep_cdouble* d_out, int32_t method,
-                                          nep_cdouble* d_mirror, int32_t nmirror, void* before_write, nep_stream stream) {
-    return orth_dev_impl(dV, ldv, rows, k, d_active_rows, dw, d_out, method, d_mirror, nmirror, before_write, nullptr, stream);
+    return orth_dev_impl(dV, ldv, rows, k, d_active_rows, dw, d_out, method, d_mirror, nmirror, nullptr, stream);
 }
 // iar's form: rows = n (k + 1); the last kernel also forms step k + 1's coefficient product d_WT (n x mt, row-major) from the
 // normalised vector and the coefficient table dC (ldc), and writes the block shift of the vector to d_shift (see k_orth_finish_vc)
 extern "C" int32_t nep_orth_dev_iar_next(const nep_cdouble* dV, int64_t ldv, int64_t n, int32_t k, const int64_t* d_active_rows,
                                          nep_cdouble* dw, nep_cdouble* d_out, int32_t method, nep_cdouble* d_mirror, int32_t nmirror,
-                                         void* before_write, const nep_cdouble* dC, int64_t ldc, int32_t mt, nep_cdouble* d_WT,
+                                         const nep_cdouble* dC, int64_t ldc, int32_t mt, nep_cdouble* d_WT,
                                          nep_cdouble* d_shift, nep_stream stream) {
     ARGCHK(dC && d_WT && d_shift && mt >= 1 && mt <= 4 && ldc >= k + 1 && n > 0);
     OrthNextVc nx; nx.C = (const cplx*)dC; nx.ldc = ldc; nx.mt = mt; nx.WT = (cplx*)d_WT; nx.shift_dst = (cplx*)d_shift; nx.n = n;
-    return orth_dev_impl(dV, ldv, n * (int64_t)(k + 1), k, d_active_rows, dw, d_out, method, d_mirror, nmirror, before_write, &nx, stream);
+    return orth_dev_impl(dV, ldv, n * (int64_t)(k + 1), k, d_active_rows, dw, d_out, method, d_mirror, nmirror, &nx, stream);
 }
 static int orth_dev_impl(const nep_cdouble* dV, int64_t ldv, int64_t rows, int32_t k,
                          const int64_t* d_active_rows, nep_cdouble* dw, nep_cdouble* d_out, int32_t method,
-                         nep_cdouble* d_mirror, int32_t nmirror, void* before_write, const OrthNextVc* next, nep_stream stream) {
+                         nep_cdouble* d_mirror, int32_t nmirror, const OrthNextVc* next, nep_stream stream) {
     ARGCHK(dV && dw && d_out);
     ARGCHK(rows > 0 && k >= 1 && ldv >= rows);
     ARGCHK(method == 0 || method == 1);
     hipStream_t st = as_stream(stream);
     const int nchunks = (int)((rows + DOT_RB - 1) / DOT_RB);
     const int nblk = (int)((rows + 63) / 64);
-    static const int npart_max = getenv("NEP_ORTH_NPART") ? std::max(64, atoi(getenv("NEP_ORTH_NPART"))) : ORTH_NPART;
-    const int npart = std::min(nblk, npart_max);
+    const int npart = std::min(nblk, ORTH_NPART);
     const int npass = method == 1 ? 1 : orth_dev_passes();
     // (a variant that formed the second pass' projections inside the first update -- one sweep over V instead of two in the 24 %
     // of the gun steps that re-orthogonalise -- was built in round 3 and measured SLOWER on the headline run, 45.0 against 42.2 ms
@@ -704,7 +695,7 @@ static int orth_dev_impl(const nep_cdouble* dV, int64_t ldv, int64_t rows, int32
     cplx* out = (cplx*)d_out;
     const size_t shm_upd = (size_t)(k + 8 * 64) * sizeof(cplx);
     // non-temporal V loads when the block that is streamed (iar: the non-zero staircase, about half of rows x k) is far larger
-    // than the last-level cache: NEP_ORTH_NT = 0 never, 1 always, unset: above NEP_ORTH_NT_MB (default 192) megabytes
+    // than the last-level cache: above 192 megabytes (orth_use_nt)
     const bool nt = orth_use_nt(rows, k, d_active_rows != nullptr);
     OrthDecide D;
     const bool rows_form = k <= orth_rows_k();
@@ -721,7 +712,6 @@ static int orth_dev_impl(const nep_cdouble* dV, int64_t ldv, int64_t rows, int32
         hipLaunchKernelGGL(k_orth_reduce_h, dim3(k), dim3(256), 0, st, nchunks, (int)k, (const cplx*)d_ph, d_c, gate, out,
                            p == 0 ? 1 : 0, p == 0 ? d_state : (int*)nullptr, OrthDecide(), 0, (const double*)d_pww, d_ww);
         LAUNCHCHK();
-        if (p == 0 && before_write) HIPCHK(hipStreamWaitEvent(st, (hipEvent_t)before_write, 0));
         if (rows_form) {
             const int nb = nb_rows;
             if (nt)

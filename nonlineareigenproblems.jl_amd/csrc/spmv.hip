@@ -407,7 +407,7 @@ __global__ __launch_bounds__(256) void k_sum_partials_d(int nb, int len, const d
 
 // ------------------------------------------------------------------------------------------
 static int xcd_swizzle() {
-    static const int v = getenv("NEP_XCD_SWIZZLE") ? atoi(getenv("NEP_XCD_SWIZZLE")) : 1;
+    static const int v = nep_env_int("NEP_XCD_SWIZZLE", 1);
     return v;
 }
 template <typename VT>
@@ -466,12 +466,12 @@ static int launch_spmv_fold(const nep_spmf* s, const cplx* v, const cplx* dC, in
 }
 
 static int fuse_max_small() {
-    static const int env = getenv("NEP_K1_FUSE_MAX") ? atoi(getenv("NEP_K1_FUSE_MAX")) : -1;
+    static const int env = nep_env_int("NEP_K1_FUSE_MAX", -1);
     return env >= 0 ? (env < 16 ? env : 16) : 16;
 }
 // 2 <= k <= fuse_max(): one launch, no W (see k_spmv_sell_kfused)
 static int fuse_max(const nep_spmf* s) {
-    static const int env = getenv("NEP_K1_FUSE_MAX") ? atoi(getenv("NEP_K1_FUSE_MAX")) : -1;
+    static const int env = nep_env_int("NEP_K1_FUSE_MAX", -1);
     if (env >= 0) return env < 16 ? env : 16;
     // small n (CSR-vector path) is launch-bound: one launch instead of two (gun k = 10: 6.8 -> 4.8 us).  At n = 1e6 the
     // k gathers per entry miss L1 and the kernel is L2-bandwidth-bound (k = 8: 90 us fused vs 64 us for k_vc + SpMV,
@@ -638,7 +638,7 @@ static int launch_vc_rows(const nep_spmf* s, int k, const cplx* dC, int64_t ldc,
 }
 // rows per workgroup of k_vc (shared with nep_spmf_plan)
 static int vc_rows(const nep_spmf* s) {
-    static const int force = getenv("NEP_VC_ROWS") ? atoi(getenv("NEP_VC_ROWS")) : 0;
+    static const int force = nep_env_int("NEP_VC_ROWS", 0);
     if (force == 16 || force == 32 || force == 64) return force;
     return s->n >= 65536 ? 64 : 32;
 }
@@ -784,11 +784,10 @@ __global__ __launch_bounds__(256) void k_spmm_rm_g(const int32_t* __restrict__ r
 // two chunks while every element offset into XT fits 32 bits, rows dealt to the XCDs in contiguous ranges on large matrices
 struct SpmmShape { int nch, grouped, xcd_rows; };
 static SpmmShape spmm_shape(const nep_spmf* s, int k, int64_t ldx, int xoff, int grid) {
-    static const int xcd_env = getenv("NEP_SPMM_XCD") ? atoi(getenv("NEP_SPMM_XCD")) : 1;
-    static const int grouped = getenv("NEP_SPMM_GROUPED") ? atoi(getenv("NEP_SPMM_GROUPED")) : 1;
+    static const int grouped = nep_env_int("NEP_SPMM_GROUPED", 1);
     SpmmShape sh;
     sh.nch = (k + 63) / 64;
-    sh.xcd_rows = (xcd_env && s->n >= 65536 && grid >= 64) ? 1 : 0;      // small matrices sit in every L2 anyway
+    sh.xcd_rows = (s->n >= 65536 && grid >= 64) ? 1 : 0;      // small matrices sit in every L2 anyway
     sh.grouped = (sh.nch <= 2 && grouped &&
                   (uint64_t)s->n * (uint64_t)ldx + (uint64_t)s->mt * (uint64_t)(xoff < 0 ? -xoff : xoff) < (1ull << 32)) ? 1 : 0;
     return sh;
@@ -974,42 +973,39 @@ int32_t nep_spmf_create(int64_t n, int32_t mt, const int32_t* const* h_rowptr, c
 }
 
 // K1 kernel choice (tuning / A-B knob): 0 = automatic, 1 = footprint tiles whenever they exist, 2 = never tiles
-static int g_k1_mode = -1;
+static int g_k1_mode = 0;
 int32_t nep_k1_set_mode(int32_t mode) { g_k1_mode = mode; return NEP_OK; }
 // K2 super-panel kernel (A-B knob, same values as NEP_K2_SP; -1 = the environment decides)
 static int g_k2_sp_mode = -1;
 int32_t nep_k2_set_sp_mode(int32_t mode) { g_k2_sp_mode = mode; return NEP_OK; }
+static const int K1_TILE_KMIN = 2, K1_TILE_KMAX = 12;      // k range of the tiled K1 on large matrices (measured, see use_tiles)
+static const int K2_TILE_KMAX = 20;                        // above: k_spmm_rm_g (0.47 ms at k = 30, tiles 0.50-0.63)
+static const int K2_SP_CM_KMIN = 9;                        // column-major K2: super-panels from this k on (see k2_cm_choice)
 static bool use_tiles(const nep_spmf* s, int k) {
     if (!s->tiles) return false;
-    if (g_k1_mode < 0) g_k1_mode = getenv("NEP_K1_MODE") ? atoi(getenv("NEP_K1_MODE")) : 0;
     if (g_k1_mode == 2) return false;
     if (nep_tiles_shmem(s->tiles, k) > 160 * 1024) return false;
     if (g_k1_mode == 1) return true;
     // measured ranges: at n = 1e6 the tiles win for 2 <= k <= 12 (no W round trip; k = 1 stays with the folded
-    // SELL SpMV, large k with k_vc + SELL whose W round trip is small against V); at gun size see NEP_K1_TILE_SMALL_KMIN
-    static const int kmin_l = getenv("NEP_K1_TILE_KMIN") ? atoi(getenv("NEP_K1_TILE_KMIN")) : 2;
-    static const int kmax_l = getenv("NEP_K1_TILE_KMAX") ? atoi(getenv("NEP_K1_TILE_KMAX")) : 12;
-    static const int kmin_s = getenv("NEP_K1_TILE_SMALL_KMIN") ? atoi(getenv("NEP_K1_TILE_SMALL_KMIN")) : (1 << 30);
-    if (s->d_sell_ptr) return k >= kmin_l && k <= kmax_l;
-    return k >= kmin_s;
+    // SELL SpMV, large k with k_vc + SELL whose W round trip is small against V); at gun size (no SELL copy) the call is
+    // launch-bound and the one-launch CSR forms stay
+    return s->d_sell_ptr != nullptr && k >= K1_TILE_KMIN && k <= K1_TILE_KMAX;
 }
 
 // K2 on the tiles: large matrices only (at gun size the wave-per-row kernel's gathers are L2 hits and it is launch-bound)
 static bool use_tiles_k2(const nep_spmf* s, int k) {
     if (!s->tiles) return false;
-    if (g_k1_mode < 0) g_k1_mode = getenv("NEP_K1_MODE") ? atoi(getenv("NEP_K1_MODE")) : 0;
     if (g_k1_mode == 2 || !nep_tiles_resid_ok(s->tiles, k)) return false;
     if (g_k1_mode == 1) return true;
     // measured at n = 1e6: 4.5x faster than the wave-per-row kernel at k = 8, 1.35x at k = 30, slower at k = 60
     // (row-major Q: a column panel of a footprint row is a 64-byte piece of a 16 k-byte row)
-    static const int kmax = getenv("NEP_K2_TILE_KMAX") ? atoi(getenv("NEP_K2_TILE_KMAX")) : 20;     // above: k_spmm_rm_g (0.47 ms at k = 30, tiles 0.50-0.63)
-    return s->d_sell_ptr != nullptr && k <= kmax;
+    return s->d_sell_ptr != nullptr && k <= K2_TILE_KMAX;
 }
 
 // K2 in super-panels (k_tile_resid_sp, spmv_tile.hip): NEP_K2_SP = 0 never, 1 (default) on large matrices (those with a SELL copy: the
 // sizes at which K2 is bound by HBM; at gun size the wave-per-row kernel's gathers are L2 hits), 2 whenever the tiles allow it (tests)
 static bool use_sp_k2(const nep_spmf* s, int k, int cm) {
-    static const int mode = getenv("NEP_K2_SP") ? atoi(getenv("NEP_K2_SP")) : 1;
+    static const int mode = nep_env_int("NEP_K2_SP", 1);
     const int m = g_k2_sp_mode >= 0 ? g_k2_sp_mode : mode;
     if (m == 0 || !s->tiles || !nep_tiles_resid_sp_ok(s->tiles, k, cm)) return false;
     return m == 2 || s->d_sell_ptr != nullptr;
@@ -1033,8 +1029,7 @@ static int k2_choice(const nep_spmf* s, int kk) {
 static int k2_cm_choice(const nep_spmf* s, int k) {
     if (!s->tiles || !nep_tiles_resid_cm_ok(s->tiles, k)) return K2_NONE;
     // (up to two panels the older kernel -- many short-lived workgroups per CU -- hides a block's start-up better: 69 against 77 us at k = 8)
-    static const int sp_cm_kmin = getenv("NEP_K2_SP_CM_KMIN") ? atoi(getenv("NEP_K2_SP_CM_KMIN")) : 9;
-    return (use_sp_k2(s, k, 1) && (k >= sp_cm_kmin || g_k2_sp_mode == 2)) ? K2_SP : K2_CM;
+    return (use_sp_k2(s, k, 1) && (k >= K2_SP_CM_KMIN || g_k2_sp_mode == 2)) ? K2_SP : K2_CM;
 }
 
 int32_t nep_spmf_tile_info(const nep_spmf* s, int64_t info[8]) {
@@ -1126,11 +1121,11 @@ int nep_mlincomb_dev_shift(nep_spmf* s, int32_t k, const nep_cdouble* dC, int64_
                            nep_cdouble* dz, nep_cdouble* d_shift, int32_t* folded, hipStream_t st) {
     *folded = 0;
     const int ch = k1_choice(s, k);
-    if (ch == K1_TILE && !getenv("NEP_NO_SHIFT_FOLD")) {      // one launch: coefficient product, SpMV and the block shift
+    if (ch == K1_TILE) {      // one launch: coefficient product, SpMV and the block shift
         *folded = 1;
         return nep_tiles_mlincomb(s->tiles, k, (const cplx*)dC, ldc, (const cplx*)dV, ldv, (cplx*)dz, (cplx*)d_shift, st);
     }
-    if (ch != K1_VC || getenv("NEP_NO_SHIFT_FOLD"))
+    if (ch != K1_VC)
         return nep_mlincomb_dev(s, k, dC, ldc, dV, ldv, dz, (nep_stream)st);
     int rc = launch_vc(s, k, (const cplx*)dC, ldc, (const cplx*)dV, ldv, st, (cplx*)d_shift);
     if (rc) return rc;

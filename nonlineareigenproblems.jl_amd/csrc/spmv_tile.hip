@@ -349,7 +349,7 @@ __global__ __launch_bounds__(256) void k_tile_resid(const TileDesc* __restrict__
 // stride of a 2-column tile -- about 0.3 ms of LDS pipe per CU however the panels are arranged; the short-lived workgroups of this
 // form overlap it best with the gathers.  Launch order (round 3, late): one-dimensional, the panels of a block back to back on ONE
 // XCD, so that the block's entries and footprint list are L2 hits for all but the first panel: 0.531 -> 0.500 ms at k = 60,
-// 0.082 -> 0.076 at k = 8 (NEP_K2_CM_ORDER=0: panels as grid.y, a block's workgroups rotate over the XCDs).
+// 0.082 -> 0.076 at k = 8 (with the panels as grid.y a block's workgroups rotate over the XCDs; the launcher no longer does that).
 template <typename VT, int MT, int PS, bool NT>
 __global__ __launch_bounds__(256) void k_tile_resid_cm(const TileDesc* __restrict__ desc, const uint32_t* __restrict__ fp,
                                                        const uint16_t* __restrict__ eidx, const VT* __restrict__ eval,
@@ -1173,8 +1173,6 @@ struct TileBuilder {
     static cplx cmake_h(double a, double b) { cplx r; r.x = a; r.y = b; return r; }
 };
 
-int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-
 }  // namespace
 
 extern "C" {
@@ -1191,11 +1189,11 @@ void nep_tiles_destroy(NepTiles* t) {
 // host part of nep_tiles_build: false when the matrix does not qualify
 static bool tiles_build_host(TileBuilder& B, int64_t n, int mt, int valbytes, const int32_t* rowptr, const uint32_t* idx,
                              const void* vals, int* stride_out, int* xp_out, int* zp_out) {
-    if (env_int("NEP_K1_TILE", 1) == 0 || mt > 8 || n < 64) return false;
+    if (nep_env_int("NEP_K1_TILE", 1) == 0 || mt > 8 || n < 64) return false;
     int tb = 0; while ((1 << tb) < mt) ++tb;
     B.n = n; B.mt = mt; B.valbytes = valbytes; B.rowptr = rowptr; B.idx = idx; B.vals = vals;
     B.lbits = 16 - tb;
-    const int lds_kb = env_int("NEP_K1_TILE_LDS_KB", 64);
+    const int lds_kb = nep_env_int("NEP_K1_TILE_LDS_KB", 64);
     B.fcap_max = std::min(1 << B.lbits, lds_kb * 1024 / (16 * mt));
     B.mark.assign(n, 0); B.loc.assign(n, 0);
     // dominant off-diagonal stride: the most frequent column offset > 1 (the line length of a 2-D grid numbering)
@@ -1223,14 +1221,14 @@ static bool tiles_build_host(TileBuilder& B, int64_t n, int mt, int valbytes, co
         }
         int tot = 0;
         for (int t = 0; t < mt; ++t) tot += cmax[t];
-        if (tot >= 1 && tot <= 8 && env_int("NEP_TILE_SLOTTED", 1)) {
+        if (tot >= 1 && tot <= 8 && nep_env_int("NEP_TILE_SLOTTED", 1)) {
             B.slot_w = tot;
             for (int t = 0; t < mt; ++t) B.slot_off[t + 1] = B.slot_off[t] + cmax[t];
             for (int t = mt; t < 8; ++t) B.slot_off[t + 1] = B.slot_off[t];
         }
     }
     const bool small = n < 32768;
-    int zp = env_int("NEP_K1_TILE_ZP", small ? 16 : 64), xp = env_int("NEP_K1_TILE_XP", small ? 4 : 8);
+    int zp = nep_env_int("NEP_K1_TILE_ZP", small ? 16 : 64), xp = nep_env_int("NEP_K1_TILE_XP", small ? 4 : 8);
     if (zp < 1) zp = 1;
     if (xp < 1) xp = 1;
     // Patch height for large grids (round 3, late): the launch runs in ROUNDS of (CUs x resident workgroups per CU) blocks, and a
@@ -1238,7 +1236,7 @@ static bool tiles_build_host(TileBuilder& B, int64_t n, int mt, int valbytes, co
     // = 1.6 rounds of 5 per CU (0.58 of the HBM roofline at k = 8), 10 x 64: 2.1 rounds of 3 (0.47), 11 x 64 / 12 x 64: 1.9 / 1.75
     // rounds of 3 (0.60-0.62).  Pick the height that minimises ceil(rounds) x resident blocks x footprint (a 5-point halo assumed).
     if (!small && stride > 0 && !getenv("NEP_K1_TILE_XP")) {
-        const int ncu = env_int("NEP_K1_TILE_NCU", 256);
+        const int ncu = 256;                                  // CUs of the MI355X
         const int zq = std::min(zp, stride);
         const int64_t X = n / stride;
         const int mtc = std::min(mt, 4);
@@ -1389,8 +1387,7 @@ static bool tile_large(const NepTiles* t) { return t->n >= 32768; }
 static void tiles_launch_shape(const NepTiles* t, int k, int* nthr, int* split) {
     *nthr = 256; *split = 0;
     if (!tile_large(t)) {
-        static const int force = env_int("NEP_K1_TILE_THREADS", 0);
-        *nthr = force ? force : (k >= 48 ? 1024 : (k >= 16 ? 512 : 256));
+        *nthr = k >= 48 ? 1024 : (k >= 16 ? 512 : 256);
         *split = (k >= 4 && ((t->fcap + 15) & ~15) * 2 <= *nthr) ? 1 : 0;
     }
 }
@@ -1398,7 +1395,7 @@ static void tiles_launch_shape(const NepTiles* t, int k, int* nthr, int* split) 
 // nep_spmf_plan) both call
 struct TileK1Shape { int nthr, split, mtc; bool nt, pf; };
 static TileK1Shape tile_k1_shape(const NepTiles* t, int k) {
-    static const int pf_on = env_int("NEP_K1_TILE_PF", 1);
+    static const int pf_on = nep_env_int("NEP_K1_TILE_PF", 1);
     TileK1Shape s;
     tiles_launch_shape(t, k, &s.nthr, &s.split);
     s.nt = tile_large(t);
@@ -1415,7 +1412,7 @@ int nep_tiles_mlincomb(const NepTiles* t, int k, const cplx* dC, int64_t ldc, co
                        cplx* d_shift, hipStream_t st) {
     const size_t shm = nep_tiles_shmem(t, k);
     if (shm > 160 * 1024) { nep_set_error("tiled K1: k = %d needs %zu bytes of LDS", k, shm); return NEP_ERR_ARG; }
-    static const int swz = env_int("NEP_XCD_SWIZZLE", 1);
+    static const int swz = nep_env_int("NEP_XCD_SWIZZLE", 1);
     const TileK1Shape sh = tile_k1_shape(t, k);
     const int nthr = sh.nthr, split = sh.split, mtc = sh.mtc;
     const bool nt = sh.nt, pf = sh.pf;
@@ -1443,7 +1440,7 @@ size_t nep_tiles_resid_shmem(const NepTiles* t, int k, int ps) {
 }
 // panel width: 8 columns when the footprint tile then still leaves room for two workgroups per CU, else 4
 int nep_tiles_resid_ps(const NepTiles* t, int k) {
-    static const int force = env_int("NEP_K2_TILE_PS", 0);
+    static const int force = nep_env_int("NEP_K2_TILE_PS", 0);
     if (force == 4 || force == 8) return force;
     return nep_tiles_resid_shmem(t, k, 8) <= 72 * 1024 ? 8 : 4;
 }
@@ -1453,7 +1450,7 @@ bool nep_tiles_resid_ok(const NepTiles* t, int k) {
 }
 
 static int tile_cm_ps() {
-    static const int ps_env = env_int("NEP_K2_CM_PS", 2);
+    static const int ps_env = nep_env_int("NEP_K2_CM_PS", 2);
     return ps_env == 8 ? 8 : (ps_env == 4 ? 4 : 2);
 }
 // partial: [nblk][2][k] doubles (|r|^2 then |q|^2 per column), or NULL; ZT (n x k row-major, ld ldz) or NULL
@@ -1466,12 +1463,10 @@ int nep_tiles_resid_cm(const NepTiles* t, int k, const cplx* dF, const cplx* Q, 
     const int ps = tile_cm_ps();
     const size_t shm = (size_t)t->fcap * ps * sizeof(cplx) + (size_t)2 * 4 * ps * sizeof(double);
     if (shm > 160 * 1024) { nep_set_error("tiled K2 (column-major): footprint too large"); return NEP_ERR_ARG; }
-    static const int swz = env_int("NEP_XCD_SWIZZLE", 1);
+    static const int swz = nep_env_int("NEP_XCD_SWIZZLE", 1);
     const bool nt = tile_large(t);
     const int npan = (k + ps - 1) / ps;
-    static const int order = env_int("NEP_K2_CM_ORDER", 1);      // 1: panels of a block back to back on one XCD (1-D launch); 0: panels as grid.y
-    const dim3 grid = order ? dim3((unsigned)(8 * ((t->nblk + 7) / 8) * npan)) : dim3((unsigned)t->nblk, (unsigned)npan);
-    const int npan_arg = order ? npan : 0;
+    const dim3 grid((unsigned)(8 * ((t->nblk + 7) / 8) * npan));     // 1-D launch: the panels of a block back to back on one XCD
 #define RC(VT, M, P, NTF)                                                                                                      \
     do {                                                                                                                       \
         if (shm > 64 * 1024) {                                                                                                 \
@@ -1479,7 +1474,7 @@ int nep_tiles_resid_cm(const NepTiles* t, int k, const cplx* dF, const cplx* Q, 
         }                                                                                                                      \
         hipLaunchKernelGGL((k_tile_resid_cm<VT, M, P, NTF>), grid, dim3(256), shm, st, (const TileDesc*)t->d_desc,             \
                            (const uint32_t*)t->d_fp, (const uint16_t*)t->d_eidx, (const VT*)t->d_eval, Q, ldq, k, dF, t->mt,   \
-                           t->fcap, t->lbits, R, ldr, partial, swz, split_row, t->nblk, npan_arg);                             \
+                           t->fcap, t->lbits, R, ldr, partial, swz, split_row, t->nblk, npan);                                 \
     } while (0)
 #define RC_M(VT, P, NTF) do { switch (t->mt) { case 1: RC(VT, 1, P, NTF); break; case 2: RC(VT, 2, P, NTF); break; case 3: RC(VT, 3, P, NTF); break; default: RC(VT, 4, P, NTF); break; } } while (0)
 #define RC_P(VT, NTF) do { if (ps == 8) RC_M(VT, 8, NTF); else if (ps == 2) RC_M(VT, 2, NTF); else RC_M(VT, 4, NTF); } while (0)
@@ -1513,12 +1508,12 @@ bool nep_tiles_resid_sp_ok(const NepTiles* t, int k, int cm) {
 // persistent form and ring of four (see the measurements in nep_tiles_resid_sp), flush mask of the slot layout
 struct TileSpShape { int nthr, fm; bool pers, ring4; };
 static TileSpShape tile_sp_shape(const NepTiles* t, int k, int cm) {
-    static const int persist = env_int("NEP_K2_SP_PERSIST", 0);
+    static const int persist = nep_env_int("NEP_K2_SP_PERSIST", 0);
     TileSpShape s;
     s.nthr = sp_threads(t);
     // NEP_K2_SP_PERSIST = 0 (default) never, 1 for 4 < k <= 12, 2 always (k > 4)
     s.pers = k > SP_PSW && (persist == 2 || (persist == 1 && k <= 3 * SP_PSW));
-    s.ring4 = cm && !s.pers && env_int("NEP_K2_SP_RING", 2) == 4;
+    s.ring4 = cm && !s.pers && nep_env_int("NEP_K2_SP_RING", 2) == 4;
     // bit j = slot j is the last of its term; the kernels exist for one term (0x80), the 5 + 2 + 1 layout (0xD0) and flushing
     // after every slot (0xFF), which is right for any layout
     int fm = 0x80;
@@ -1532,13 +1527,13 @@ int nep_tiles_resid_sp(const NepTiles* t, int k, const cplx* dF, const cplx* Q, 
     const TileSpShape sh = tile_sp_shape(t, k, cm);
     const int nthr = sh.nthr;
     const size_t shm = sp_shmem(t, nthr) + (size_t)SP_FPAD(nthr) * 4;          // (+ the second footprint list of the persistent form)
-    static const int swz = env_int("NEP_XCD_SWIZZLE", 1);
+    static const int swz = nep_env_int("NEP_XCD_SWIZZLE", 1);
     // persistent form (k_tile_resid_spp) from two panels on: one workgroup per CU (the tiles leave room for one), a multiple of 8
     static int ncu = 0;
     if (!ncu) {
         int dev = 0; hipDeviceProp_t pr;
         ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount >= 8) ? pr.multiProcessorCount : 256;
-        ncu = env_int("NEP_K2_SP_GRID", ncu) / 8 * 8;
+        ncu = ncu / 8 * 8;
         if (ncu < 8) ncu = 8;
     }
     // measured at n = 1e6 (kernel time, rocprofv3): k = 8 persistent 58.6 us / one block per workgroup 64.6 us (the old kernel: 59.4);
@@ -1601,7 +1596,7 @@ int nep_tiles_resid(const NepTiles* t, int k, const cplx* dF, const cplx* QT, in
     const int ps = nep_tiles_resid_ps(t, k);
     const size_t shm = nep_tiles_resid_shmem(t, k, ps);
     if (t->mt > 4 || shm > 160 * 1024) { nep_set_error("tiled K2: mt = %d, k = %d not supported", t->mt, k); return NEP_ERR_ARG; }
-    static const int swz = env_int("NEP_XCD_SWIZZLE", 1);
+    static const int swz = nep_env_int("NEP_XCD_SWIZZLE", 1);
     const bool nt = tile_large(t);
 #define RL(VT, M, P, NTF)                                                                                                      \
     do {                                                                                                                       \

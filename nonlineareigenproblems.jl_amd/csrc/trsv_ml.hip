@@ -859,7 +859,7 @@ void transpose_pattern(int64_t n, const int32_t* cp, const int32_t* ri, std::vec
         }
 }
 
-int bmax_env() { const char* e = getenv("NEP_ML_BMAX"); const int v = e ? atoi(e) : -1; return (v >= 8 && v <= ML_BMAX) ? v : -1; }
+int bmax_env() { const int v = nep_env_int("NEP_ML_BMAX", -1); return (v >= 8 && v <= ML_BMAX) ? v : -1; }
 int bmax_of_level(int lev, int64_t n, int forced) {
     if (forced > 0) return forced;
     if (n > 200000 && lev == 0) return 64;          // most rows sit in level 0: 16*b/2 bytes of inverse per row
@@ -1134,7 +1134,7 @@ static int ml_build_apex_dense(MLFactor* F, hipStream_t bst);
 static int choose_apex(const MLSym* S, int expected_solves);
 // end of a numeric build on bst: `ready` = block inverses done (solves may start), then the apex behind it
 static int ml_finish_numeric(MLFactor* F, hipStream_t bst) {
-    static const int apex_sync = getenv("NEP_ML_APEX_SYNC") ? atoi(getenv("NEP_ML_APEX_SYNC")) : 0;
+    static const int apex_sync = nep_env_int("NEP_ML_APEX_SYNC", 0);
     F->apex_live = false;
     F->solves_since_numeric = 0;
     F->synced_valid = false;
@@ -1143,7 +1143,7 @@ static int ml_finish_numeric(MLFactor* F, hipStream_t bst) {
     // finished BEFORE the first solve (apex from solve 1); 2 (default) = the dense build behind `ready`, the switch at solve NEP_ML_APEX_AT:
     // measured on the headline call 37.0 / 35.0-35.8 / 34.5 ms (the 1.07 ms build next to the first five solves disturbs them far less than
     // the sparse one did, and nothing waits for it)
-    static const int apex_dense = getenv("NEP_ML_APEX_DENSE") ? atoi(getenv("NEP_ML_APEX_DENSE")) : 2;
+    static const int apex_dense = nep_env_int("NEP_ML_APEX_DENSE", 2);
     if (F->apex_la > 0 && apex_dense == 2) {    // dense build behind `ready`, switch at solve NEP_ML_APEX_AT like the sparse build
         HIPCHK(hipEventRecord(F->ready, bst));
         int rc = ml_build_apex_dense(F, bst);
@@ -1369,10 +1369,10 @@ static int ml_numeric_dev(MLFactor* F, const cplx* d_Lx, const cplx* d_Ux, hipSt
     hipLaunchKernelGGL(k_ml_gather, dim3(gu), dim3(256), 0, bst, S->nnzU, (const int32_t*)S->U.d_map, d_Ux, F->d_vals, oU, oUb, oD);
     LAUNCHCHK();
     // the two block-inverse builds are independent (and each a chain of dependent in-block levels that leaves most of the GPU idle):
-    // the U side runs on a second build stream next to the L side (NEP_ML_INV_2STREAM=0: one after the other)
-    static const int two = getenv("NEP_ML_INV_2STREAM") ? atoi(getenv("NEP_ML_INV_2STREAM")) : 1;
-    hipStream_t bst2 = two ? g_bstreams.get() : bst;
-    if (bst2 == bst || !bst2) bst2 = bst;
+    // the U side runs on a second build stream next to the L side (one after the other on one stream: iar median 44.4-44.9
+    // against 44.0 ms, C4 0.128-0.130 against 0.121-0.126 s)
+    hipStream_t bst2 = g_bstreams.get();
+    if (!bst2) bst2 = bst;
     if (bst2 != bst) {
         hipEvent_t ev; HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         HIPCHK(hipEventRecord(ev, bst)); HIPCHK(hipStreamWaitEvent(bst2, ev, 0)); (void)hipEventDestroy(ev);
@@ -1964,7 +1964,7 @@ static int run_apex(const MLSolveCtx& c, hipStream_t st, int* launches) {
         return NEP_OK;
     }
 #define APEX_GEMV(RB_) hipLaunchKernelGGL((k_apex_gemv<RB_>), dim3((unsigned)((T + 3) / 4), (c.nrhs + RB_ - 1) / RB_), dim3(256), 0, st, P)
-    const int gemv1 = getenv("NEP_ML_GEMV1") ? atoi(getenv("NEP_ML_GEMV1")) : 1;
+    const int gemv1 = nep_env_int("NEP_ML_GEMV1", 1);
     if (c.nrhs >= 8) APEX_GEMV(8); else if (c.nrhs >= 2) APEX_GEMV(4);
     else if (gemv1 && T <= ML_APEX_TMAX) hipLaunchKernelGGL(k_apex_gemv1, dim3((unsigned)((T + 7) / 8)), dim3(256), 0, st, P);
     else APEX_GEMV(1);
@@ -2209,7 +2209,7 @@ int ml_solve(MLFactor* F, int nrhs, const nep_cdouble* dB, int64_t ldb, const ne
     // iar call: 38.5 ms at 4 ... 8, 38.9-39.8 at 1, 39.5-40.2 at 12, 41.4 at 40: a short wait while the build has the device to
     // itself beats both more solves through the apex levels and an immediate wait.  NEP_ML_APEX_AT=0: as soon as a query finds the
     // build finished (round 2).
-    static const int apex_at = getenv("NEP_ML_APEX_AT") ? atoi(getenv("NEP_ML_APEX_AT")) : 6;
+    static const int apex_at = nep_env_int("NEP_ML_APEX_AT", 6);
     if (F->apex_la > 0 && !F->apex_live && F->apex_ev) {
         bool take = false;
         if (apex_at > 0) take = F->solves_since_numeric >= apex_at;
@@ -2243,7 +2243,7 @@ int ml_solve(MLFactor* F, int nrhs, const nep_cdouble* dB, int64_t ldb, const ne
         return NEP_ERR_HIP;
     }
     // MEASURED NEGATIVE (kept opt-in, NEP_ML_FUSE=1, so that it can be reproduced): on the gun factors the one-launch form
-    // takes 770 us per solve against 38 us for the five launches (470 us without the ticket atomics, NEP_ML_FUSE_MODE=1).
+    // takes 770 us per solve against 38 us for the five launches (470 us without the ticket atomics, mode bit 0 of k_ml_fused).
     // The 8 XCDs have no common L2, so every agent-scope atomic on the phase counters is performed memory-side; ~3000
     // same-address increments per solve serialise at ~150 ns each, and the release/acquire fences are the same L2
     // write-back/invalidate a kernel boundary performs.  A kernel boundary (~2.5 us on this part) IS the cheap grid barrier.
@@ -2265,7 +2265,7 @@ int ml_solve(MLFactor* F, int nrhs, const nep_cdouble* dB, int64_t ldb, const ne
                 HIPCHK(hipHostGetDevicePointer((void**)&F->d_ferr, F->h_ferr, 0));
                 *F->h_ferr = 0; F->fuse_epoch = 0;
             }
-            rec.a.mode = getenv("NEP_ML_FUSE_MODE") ? atoi(getenv("NEP_ML_FUSE_MODE")) : 0; rec.a.pad0 = 0;
+            rec.a.mode = 0; rec.a.pad0 = 0;
             rec.a.ctr = F->d_fctr; rec.a.epoch = F->fuse_epoch++; rec.a.err = F->d_ferr;
             hipLaunchKernelGGL(k_ml_fused, dim3((unsigned)rec.a.total), dim3(256), 0, st, rec.a);
             LAUNCHCHK();

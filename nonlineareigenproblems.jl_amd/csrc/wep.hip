@@ -51,7 +51,8 @@ __device__ __forceinline__ int tpos(int x, const TLay tl) {
 
 // workgroup -> column group, XCD-contiguous (workgroup id % 8 = XCD): the groups an XCD works on at one time are neighbours in x, so
 // the 64-byte pieces they write to (read from) one mode row of the transposed block are neighbours too -- its L2 sees 2 KB runs per
-// row instead of every other 64-byte piece of a line belonging to another XCD (NEP_WEP_DFT_XCD=0: group = workgroup id as before)
+// row instead of every other 64-byte piece of a line belonging to another XCD (the launchers pass xcd_order = WEP_DFT_XCD_ORDER = 1; 0: group = workgroup id)
+static const int WEP_DFT_XCD_ORDER = 1;
 __device__ __forceinline__ int dft_group(int xcd_order) {
     const int b = blockIdx.x, nb = gridDim.x;
     if (!xcd_order) return b;
@@ -138,7 +139,7 @@ __global__ __launch_bounds__(1024) void k_dft_cols(int nz, int nx, int N1, int N
 // k1+2 G1) of one n2, stage 2 (k2, k2+G2, k2+2 G2) of one k1 -- so one 64-byte read of the four columns feeds 12 complex
 // multiply-adds instead of 4 (the one-output-per-thread form moves 80 bytes of LDS per 32 flops and is LDS-bound at 35 us;
 // this one moves 112 bytes per 96 flops).  Measured at 999 x 1003: 31.5 / 33.5 us (forward / inverse) against 35.8 / 34.0 us -- the kernel
-// is bound by exposed latency (one 128 KB workgroup per CU, six waves), not by LDS bytes; `NEP_WEP_DFT_RB=0` selects the old form.
+// is bound by exposed latency (one 128 KB workgroup per CU, six waves), not by LDS bytes.  k_dft_cols remains for the column counts this form does not have (2, 1).
 #ifdef WEP_PROF
 __device__ unsigned long long g_dft_prof[16];
 extern "C" int32_t nep_wep_prof_read(unsigned long long* out, int32_t reset) {
@@ -868,8 +869,7 @@ int32_t nep_wep_sylv_create(int32_t nz, int32_t nx, const nep_cdouble* h_d, doub
     int N1 = nz, N2 = 1;
     for (int a = 2; a * a <= nz; ++a)
         if (nz % a == 0 && std::gcd(a, nz / a) == 1 && a + nz / a < N1 + N2) { N1 = nz / a; N2 = a; }
-    int cols = getenv("NEP_WEP_DFT_COLS") ? std::max(1, std::min(4, atoi(getenv("NEP_WEP_DFT_COLS")))) : 4;
-    if (cols == 3) cols = 2;
+    int cols = 4;          // columns per workgroup: 4 while they fit the LDS, else 2, else 1
     while (cols > 1 && ((size_t)2 * cols * nz + N1 + N2) * sizeof(cplx) > 150 * 1024) cols >>= 1;
     if (((size_t)2 * cols * nz + N1 + N2) * sizeof(cplx) > 150 * 1024) {
         nep_set_error("nep_wep_sylv_create: nz = %d does not fit the LDS staging of the DFT kernel", nz);
@@ -982,8 +982,7 @@ static int32_t pinv_apply_impl(nep_wep_pinv* p, const nep_cdouble* d_sinv, const
                                const cplx* gX, int gnx, double gd1, double gd2) {
     static thread_local bool attr_set = false;
     if (!attr_set) { HIPCHK(hipFuncSetAttribute((const void*)k_wep_pinv, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); attr_set = true; }
-    static const bool sym_on = !(getenv("NEP_WEP_PINV_SYM") && atoi(getenv("NEP_WEP_PINV_SYM")) == 0);
-    if (sym_on && (p->N1 & 1) && (p->N2 & 1) && p->N1 >= 3 && p->N2 >= 3) {
+    if ((p->N1 & 1) && (p->N2 & 1) && p->N1 >= 3 && p->N2 >= 3) {
         const int items = std::max((p->N1 - 1) / 2 * p->N2, (p->N2 - 1) / 2 * p->N1);
         if (items <= 512) {
             hipLaunchKernelGGL(k_wep_pinv_sym, dim3(2), dim3((items + 63) / 64 * 64), ((size_t)2 * p->nz + p->N1 + p->N2) * sizeof(cplx),
@@ -1056,7 +1055,7 @@ int32_t nep_wep_sylv_solve(nep_wep_sylv* s, nep_cdouble* dX, nep_stream stream) 
     static thread_local bool attr_set = false;
     if (!attr_set) {
 #define DFT_ATTR(F_, C_) HIPCHK(hipFuncSetAttribute((const void*)k_dft_cols<F_, C_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024))
-        DFT_ATTR(true, 4); DFT_ATTR(false, 4); DFT_ATTR(true, 2); DFT_ATTR(false, 2); DFT_ATTR(true, 1); DFT_ATTR(false, 1);
+        DFT_ATTR(true, 2); DFT_ATTR(false, 2); DFT_ATTR(true, 1); DFT_ATTR(false, 1);
         HIPCHK(hipFuncSetAttribute((const void*)k_dft_cols_rb<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
         HIPCHK(hipFuncSetAttribute((const void*)k_dft_cols_rb<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
 #undef DFT_ATTR
@@ -1069,16 +1068,15 @@ int32_t nep_wep_sylv_solve(nep_wep_sylv* s, nep_cdouble* dX, nep_stream stream) 
 #define DFT_LAUNCH(F_, C_, SGN_, SRC_, DST_)                                                                               \
     hipLaunchKernelGGL((k_dft_cols<F_, C_>), grid, dim3(threads), shm, st, nz, nx, s->N1, s->N2, (const int32_t*)s->d_in,    \
                        (const int32_t*)s->d_out, (const cplx*)s->d_w1, (const cplx*)s->d_w2, SGN_, scale, SRC_, DST_, xcd_order, tl)
-    static const int xcd_order = getenv("NEP_WEP_DFT_XCD") ? atoi(getenv("NEP_WEP_DFT_XCD")) : 1;
-    static const int rb = getenv("NEP_WEP_DFT_RB") ? atoi(getenv("NEP_WEP_DFT_RB")) : 1;
+    const int xcd_order = WEP_DFT_XCD_ORDER;
 #define DFT_BY_COLS(F_, SGN_, SRC_, DST_)                                                                                  \
-    do { if (s->cols == 4 && rb)                                                                                            \
+    do { if (s->cols == 4)                                                                                                  \
              hipLaunchKernelGGL((k_dft_cols_rb<F_>), grid, dim3(384), shm, st, nz, nx, s->N1, s->N2, (const int32_t*)s->d_in, \
                                 (const int32_t*)s->d_in_inv, (const int32_t*)s->d_out, (const cplx*)s->d_w1, (const cplx*)s->d_w2, SGN_, scale, SRC_, DST_, xcd_order, tl); \
-         else if (s->cols == 4) DFT_LAUNCH(F_, 4, SGN_, SRC_, DST_); else if (s->cols == 2) DFT_LAUNCH(F_, 2, SGN_, SRC_, DST_);  \
+         else if (s->cols == 2) DFT_LAUNCH(F_, 2, SGN_, SRC_, DST_);                                                         \
          else DFT_LAUNCH(F_, 1, SGN_, SRC_, DST_); } while (0)
     // symmetric-half form of the two dense stages (odd N1, N2): NEP_WEP_DFT_SYM = "cols*10 + kb" (42, 43, 22, 23) or 0 = off
-    static const int symcfg = getenv("NEP_WEP_DFT_SYM") ? atoi(getenv("NEP_WEP_DFT_SYM")) : 22;
+    static const int symcfg = nep_env_int("NEP_WEP_DFT_SYM", 22);
     int sym_cols = symcfg / 10, sym_kb = symcfg % 10, sym_threads = 0;
     if (symcfg && (s->N1 & 1) && (s->N2 & 1) && s->N1 >= 3 && s->N2 >= 3 && (sym_cols == 2 || sym_cols == 4) && (sym_kb == 2 || sym_kb == 3)) {
         const int H1 = (s->N1 - 1) / 2, H2 = (s->N2 - 1) / 2;
@@ -1148,7 +1146,7 @@ int32_t nep_wep_sylv_solve(nep_wep_sylv* s, nep_cdouble* dX, nep_stream stream) 
 }  // extern "C"
 struct SymCfg { int cols = 0, kb = 0, threads = 0; size_t shm = 0; unsigned grid = 0; };
 static bool sylv_sym_cfg(const nep_wep_sylv* s, SymCfg& c) {
-    static const int symcfg = getenv("NEP_WEP_DFT_SYM") ? atoi(getenv("NEP_WEP_DFT_SYM")) : 22;
+    static const int symcfg = nep_env_int("NEP_WEP_DFT_SYM", 22);
     c.cols = symcfg / 10; c.kb = symcfg % 10;
     if (!(symcfg && (s->N1 & 1) && (s->N2 & 1) && s->N1 >= 3 && s->N2 >= 3 && (c.cols == 2 || c.cols == 4) && (c.kb == 2 || c.kb == 3)))
         return false;
@@ -1163,7 +1161,7 @@ static bool sylv_sym_cfg(const nep_wep_sylv* s, SymCfg& c) {
 template <bool FWD, int EXPAND>
 static int32_t sylv_dft_sym_launch(nep_wep_sylv* s, const SymCfg& c, double sgn, const cplx* src, cplx* dst, hipStream_t st, DftExpand ex,
                                    int batch = 1) {
-    static const int xcd_order = getenv("NEP_WEP_DFT_XCD") ? atoi(getenv("NEP_WEP_DFT_XCD")) : 1;
+    const int xcd_order = WEP_DFT_XCD_ORDER;
     const double scale = 1.0 / sqrt((double)s->nz);
     const TLay tl{s->ldt, s->lseg};
 #define SYMX(C_, K_)                                                                                                          \
@@ -1289,7 +1287,7 @@ int32_t nep_wep_smw_matrix_modes(nep_wep_sylv* s, nep_wep_pinv* p, int32_t N, co
     hipStream_t st = as_stream(stream);
     const int nz = s->nz, mm = N * (N + 4), L = nz / N;
     const int64_t tsz = (int64_t)nz * s->ldt, ssz = (int64_t)nz * (N + 4);
-    int B = getenv("NEP_WEP_SMW_BATCH") ? atoi(getenv("NEP_WEP_SMW_BATCH")) : 16;
+    int B = 16;            // columns of the matrix per launch (while the batch of transformed blocks stays within 1 GiB)
     B = std::max(1, std::min(B, (int)std::max<int64_t>(1, ((int64_t)1 << 30) / (tsz * (int64_t)sizeof(cplx)))));
     cplx* work = nullptr;
     int32_t rc = nep_pool_alloc((void**)&work, ((size_t)B * (tsz + ssz) + mm + 4 * (size_t)nz) * sizeof(cplx));

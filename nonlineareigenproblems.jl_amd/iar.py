@@ -15,7 +15,6 @@ Reference step (method_iar.jl:94-164)            device realisation
   Q=VV[1:n,:]*Z                                   K7 nep_gemm_ts -> row-major Q^T
   err[k,s]=estimate_error(...) for s=1:k          K2 nep_resid_batch (one pass for all k pairs)
 """
-import os
 import threading
 import time
 
@@ -23,6 +22,7 @@ import numpy as np
 import torch
 
 from . import dense, _hosteig
+from ._env import env_flag, env_float, env_int, env_str
 from ._lib import lib, check, c_vp, c_i32, NepError, NEP_ERR_BREAKDOWN
 from .errmeasure import DefaultErrmeasure, estimate_errors, estimate_errors_async
 from .exceptions import NoConvergenceException
@@ -93,10 +93,10 @@ def _check_stream():
     dev = torch.cuda.current_device()
     st = _CHECK_STREAMS.get(dev)
     if st is None:
-        # the convergence checks are off the critical path: their stream gets the LOWEST priority the device offers, so that
-        # the dispatcher serves the recurrence's kernels first when both streams have work (NEP_IAR_CHECK_PRIO overrides;
-        # torch clamps to the device's range, a lower number is a higher priority)
-        st = _CHECK_STREAMS[dev] = torch.cuda.Stream(priority=int(os.environ.get("NEP_IAR_CHECK_PRIO", "1")))
+        # the convergence checks are off the critical path: their stream asks for the LOWEST priority the device offers, so that
+        # the dispatcher serves the recurrence's kernels first when both streams have work (torch clamps to the device's
+        # range, a lower number is a higher priority)
+        st = _CHECK_STREAMS[dev] = torch.cuda.Stream(priority=1)
     return st
 
 
@@ -115,19 +115,17 @@ def _eig_streams(count, others=()):
     if len(sts) >= count:
         return sts[:count]
     import ctypes as _C
-    cands = [torch.cuda.Stream(priority=int(os.environ.get("NEP_IAR_EIG_PRIO", "0"))) for _ in range(int(os.environ.get("NEP_IAR_EIG_CANDIDATES", "8")))]
-    probe = os.environ.get("NEP_IAR_EIG_PROBE", "1") != "0"
+    cands = [torch.cuda.Stream(priority=0) for _ in range(8)]
     for c in cands:
         if len(sts) >= count:
             break
         ok = True
-        if probe:
-            for o in list(others) + sts:
-                r = c_i32(0)
-                check(lib.nep_stream_pair_serializes(c_vp(o.cuda_stream), c_vp(c.cuda_stream), _C.byref(r)))
-                if r.value:
-                    ok = False
-                    break
+        for o in list(others) + sts:
+            r = c_i32(0)
+            check(lib.nep_stream_pair_serializes(c_vp(o.cuda_stream), c_vp(c.cuda_stream), _C.byref(r)))
+            if r.value:
+                ok = False
+                break
         if ok:
             sts.append(c)
     while len(sts) < count:              # no free hardware queue: better a shared one than none
@@ -267,9 +265,9 @@ def _iar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
     # ---- the one-call route: pure SPMF operator, device LU, DGKS / CGS, an error measure the library evaluates itself
     M0inv = None
     if (_native_run and _native_step and not _force_sync and timers is None and not proj_solve and m <= dense.HESS_EIG_KMAX
-            and dense._orth_code(orthmethod) in (0, 1) and os.environ.get("NEP_IAR_NATIVE_RUN", "1") != "0"
-            and not any(os.environ.get(e) for e in ("NEP_IAR_SYNC", "NEP_IAR_PYSTEP", "NEP_IAR_TRACE", "NEP_IAR_ONE_STREAM", "NEP_IAR_PASSES"))
-            and os.environ.get("NEP_IAR_EIG", "dev") != "host"):
+            and dense._orth_code(orthmethod) in (0, 1) and env_str("NEP_IAR_NATIVE_RUN", "1") != "0"
+            and not any(env_flag(e) for e in ("NEP_IAR_SYNC", "NEP_IAR_PYSTEP", "NEP_IAR_TRACE", "NEP_IAR_ONE_STREAM", "NEP_IAR_PASSES"))
+            and env_str("NEP_IAR_EIG", "dev") != "host"):
         from .linsolvers import FactorizeLinSolver
         from .nep import AbstractSPMF
         errkind = _native_errmeasure(errmeasure, nep)
@@ -314,7 +312,7 @@ def _iar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
     # worker waits for, the residual norms of the Ritz pairs come back the same way (nep_resid_batch_dev) -- the host
     # enqueues step k+1.. while the device is still executing step k.  `timers` (instrumented run), MGS and
     # NEP_IAR_SYNC=1 use the step-synchronous loop; both produce the same iterates.
-    use_async = (timers is None and dense._orth_code(orthmethod) in (0, 1) and not os.environ.get("NEP_IAR_SYNC")
+    use_async = (timers is None and dense._orth_code(orthmethod) in (0, 1) and not env_flag("NEP_IAR_SYNC")
                  and not proj_solve and not _force_sync)
     pnep = None
     if proj_solve:                                       # method_iar.jl:89-92
@@ -342,7 +340,7 @@ def _iar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
     # read back inside a step: the step records omega of every iterate behind the H row and fill_H replays UMFPACK's
     # stopping rule on the record (FactorizeLinSolver.review_recorded); a miss re-runs the call with checked solves.
     cstep = None
-    if use_async and _native_step and not os.environ.get("NEP_IAR_PYSTEP"):
+    if use_async and _native_step and not env_flag("NEP_IAR_PYSTEP"):
         from .linsolvers import FactorizeLinSolver
         from .nep import AbstractSPMF
         import ctypes as _C
@@ -373,11 +371,11 @@ def _iar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
     from ._affinity import cpu_budget
     # host eig of up to LAG+1 consecutive steps in flight: as many workers as the CPU budget of this rank allows (measured on
     # gun, 16-CPU budget: LAG 3 -> 86 ms per run, 5 -> 75, 9 -> 72, 15 -> 73)
-    LAG = int(os.environ.get("NEP_IAR_LAG", str(max(1, min(12, cpu_budget() - 3)))))
+    LAG = env_int("NEP_IAR_LAG", max(1, min(12, cpu_budget() - 3)))
     pool = ThreadPoolExecutor(max_workers=LAG + 1)
     state = {"lam": lam, "QT": QT, "idx": idx, "conv_eig": 0, "k_checked": 0}
 
-    trace = {} if os.environ.get("NEP_IAR_TRACE") else None
+    trace = {} if env_flag("NEP_IAR_TRACE") else None
     plans = [0] * (m + 1)
     t_marks.append(("pool", time.perf_counter()))
 
@@ -499,16 +497,16 @@ def _iar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
     # second stream next to the Arnoldi recurrence (latency-bound small kernels at gun size) instead of in line with it.
     # Only with the native step: there this thread touches none of the scratch the checks use (csrc/spmv.hip: coef / part /
     # ring belong to the residual batch, cwpart / cwring to the refinement inside the step).
-    check_thread = cstep is not None and not os.environ.get("NEP_IAR_ONE_STREAM") and hasattr(errmeasure, "batch_async")
+    check_thread = cstep is not None and not env_flag("NEP_IAR_ONE_STREAM") and hasattr(errmeasure, "batch_async")
     # ONE check stream per device for the life of the process: torch's caching allocator keeps freed blocks per stream, and a
     # fresh stream per call (32 of them in torch's pool) made every stream build its own cache of Ritz blocks
-    check_stream = _check_stream() if (check_thread and not os.environ.get("NEP_IAR_CHECK_MAIN_STREAM")) else None
+    check_stream = _check_stream() if check_thread else None
 
     # eigen-decompositions on the device (csrc/hesseig.hip) instead of LAPACK on host worker threads: no eig thread, no waiter
     # per step -- 133 ms of host CPU per headline call gone; NEP_IAR_EIG=host keeps the round-3 route (and is the fallback for
     # maxit beyond the LDS-resident limit, or when a decomposition reports a failure)
     dev_eig = (check_thread and check_stream is not None and m <= dense.HESS_EIG_KMAX
-               and os.environ.get("NEP_IAR_EIG", "dev") != "host")
+               and env_str("NEP_IAR_EIG", "dev") != "host")
     # its stream: one whose hardware queue is shared neither with this thread's stream nor with the check stream (probed once
     # per process and device, on this thread, before the first step is enqueued)
     eig_stream = _eig_streams(1, others=(torch.cuda.current_stream(), check_stream))[0] if dev_eig else None
@@ -543,7 +541,7 @@ def _iar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
     # spinning worker threads slow the launching thread down: pin BLAS to one thread for the duration of the loop
     import nep_amd_hostlu as _nep_hostlu
     ctl = _nep_hostlu.blas_controller()
-    blas_guard = ctl.limit(limits=1) if (ctl is not None and os.environ.get("NEP_IAR_BLAS_GUARD", "1") != "0") else None
+    blas_guard = ctl.limit(limits=1) if ctl is not None else None
     if blas_guard is not None:
         blas_guard.__enter__()
     t_marks.append(("blas", time.perf_counter()))
@@ -557,9 +555,9 @@ def _iar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
             # neigs = Inf: the iteration always runs to maxit, nothing the recurrence does ahead of the checks can be wasted,
             # so it is not throttled at all (the eigen-decompositions of the last steps -- half of all eig time -- then
             # queue up behind the device instead of pacing it)
-            unthrottled = np.isinf(neigs) and not os.environ.get("NEP_IAR_THROTTLE")
+            unthrottled = np.isinf(neigs)
             # (device decompositions go out in batches of up to NEP_IAR_EIG_BATCH steps: the look-ahead is that batch, whatever the CPU budget)
-            slots = threading.Semaphore(m + 1 if unthrottled else (max(LAG + 1, int(os.environ.get("NEP_IAR_EIG_BATCH", "16"))) if dev_eig else LAG + 1))
+            slots = threading.Semaphore(m + 1 if unthrottled else (max(LAG + 1, env_int("NEP_IAR_EIG_BATCH", 16)) if dev_eig else LAG + 1))
 
             def checker():
                 inflight = deque()
@@ -604,10 +602,10 @@ def _iar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
                 kernel; only the inverse iterations are still running) the host forms lambda = sigma + gamma / D and f_t(lambda)
                 per step and enqueues Ritz GEMM (B operand = the device eigenvector block) + residual batch on the check stream.
                 (C) The 2 kc norms come back behind another event.  One thread polls the event queues; no LAPACK, no waiters."""
-                BMAX = max(1, int(os.environ.get("NEP_IAR_EIG_BATCH", "16")))
-                LASTB = max(1, int(os.environ.get("NEP_IAR_EIG_LAST", "8")))
-                T100 = float(os.environ.get("NEP_IAR_EIG_MS100", "3.3"))     # ms of one decomposition at k = 100 (scales as k^2)
-                TSTEP = float(os.environ.get("NEP_IAR_EIG_MSSTEP", "0.35"))  # ms per Arnoldi step (gun, k ~ 100)
+                BMAX = max(1, env_int("NEP_IAR_EIG_BATCH", 16))
+                LASTB = max(1, env_int("NEP_IAR_EIG_LAST", 8))
+                T100 = env_float("NEP_IAR_EIG_MS100", 3.3)     # ms of one decomposition at k = 100 (scales as k^2)
+                TSTEP = 0.35                                  # ms per Arnoldi step (gun, k ~ 100)
                 est = eig_stream
                 wsz = (dense.hess_eig_worksize(m) + 15) // 16 * 16
                 work = _eig_work_acquire(BMAX * wsz)
@@ -616,8 +614,8 @@ def _iar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
                 wnp = wpin.numpy()
                 pendA = deque(); stA = deque(); stC = deque()
                 done = False
-                t_poll = float(os.environ.get("NEP_IAR_POLL_US", "30")) * 1e-6
-                force_fail = int(os.environ.get("NEP_IAR_EIG_FAIL_AT", "0"))   # tests: treat this step's decomposition as failed
+                t_poll = 30e-6
+                force_fail = env_int("NEP_IAR_EIG_FAIL_AT", 0)   # tests: treat this step's decomposition as failed
                 # Batch plan.  A batch occupies the eig stream for the time of its LARGEST decomposition whatever its size, and
                 # cannot start before its last step has run: batches of about twice (decomposition time / step time) steps keep
                 # the stream half idle, so the last batch starts the moment step m is done; that last batch is kept smaller,
@@ -654,7 +652,7 @@ def _iar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
                         mrow = c_vp(wpin.data_ptr() + 16 * (k0 - 1) * (m + 2))
                         rc_ = lib.nep_hess_eigvals_batch_dev(nb, k0, kstep, c_vp(Hdev.data_ptr()), m + 4, wrow, kstep * (m + 2),
                                                             c_vp(work.data_ptr()), wsz, mrow, kstep * (m + 2), sp_)
-                        if rc_ != 0 or os.environ.get("NEP_IAR_EIG_LAUNCH_FAIL"):
+                        if rc_ != 0 or env_flag("NEP_IAR_EIG_LAUNCH_FAIL"):
                             # the launch itself was refused (e.g. a device that does not grant the kernel's 160 KB of LDS): not a
                             # reason to abort the run -- the batch's decompositions go to LAPACK on the host (host_redo), behind an
                             # event that says its last step has run
@@ -761,7 +759,7 @@ def _iar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
             try:
                 BATCH = max(1, min(4, LAG // 2))
                 if unthrottled:
-                    BATCH = int(os.environ.get("NEP_IAR_BATCH", "8"))
+                    BATCH = 8
                 while k <= m and state["conv_eig"] < neigs and not failure:
                     # as many steps as there are free check slots (at most BATCH) go to the device in ONE foreign call: the
                     # interpreter lock is released for all of it and re-acquired once (with one call per step this thread
@@ -844,7 +842,7 @@ def _iar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
             print("iar trace (ms after entry): setup %.1f (%s) | " % ((t_setup_done - t_entry) * 1e3, " ".join("%s %.2f" % (a_, (b_ - t_entry) * 1e3) for a_, b_ in t_marks))
                   + " ".join("k=%d enq %.1f dev %.1f" % (kk, (trace["enq_%d" % kk] - t_entry) * 1e3, (trace["dev_done_%d" % kk] - t_entry) * 1e3) for kk in ks)
                   + " | end %.1f | native steps %d, %.1f ms inside nep_iar_step; checker: wait eig %.1f launch %.1f consume %.1f ms" % ((t_end - t_entry) * 1e3, trace.get("native_n", 0), trace.get("native_s", 0.0) * 1e3, trace.get("chk_wait", 0) * 1e3, trace.get("chk_launch", 0) * 1e3, trace.get("chk_consume", 0) * 1e3))
-        if use_async and os.environ.get("NEP_IAR_PASSES"):
+        if use_async and env_flag("NEP_IAR_PASSES"):
             torch.cuda.synchronize()
             print("orth passes per step:", [int(Hnp[j - 1][j + 1].real) for j in range(1, m + 1)], "flags",
                   [int(Hnp[j - 1][j + 1].imag) for j in range(1, m + 1)])

@@ -21,6 +21,7 @@ import scipy.sparse as sp
 import torch
 
 from . import _lib
+from ._env import env_float, env_int, env_str
 from ._lib import lib, check, hptr, c_vp, c_i64
 from .nep import CDT, to_dev, to_host, is_dev, stream_ptr
 
@@ -49,7 +50,7 @@ class HostLUPool:
             return cls._pool                    # whatever size it was started with
         if workers is None:
             from ._affinity import cpu_budget
-            workers = int(os.environ.get("NEP_HOSTLU_WORKERS", min(16, max(1, cpu_budget() - 2))))
+            workers = env_int("NEP_HOSTLU_WORKERS", min(16, max(1, cpu_budget() - 2)))
         if cls._pool is None or cls._workers != workers:
             cls.shutdown()
             import multiprocessing as mp
@@ -76,7 +77,7 @@ class HostLUPool:
                 ctx = mp.get_context("spawn")
                 # one physical core per worker, taken from the END of the allowed set (the launching thread, the eig and
                 # builder threads of this process stay on the first cores); NEP_HOSTLU_PIN=0 leaves placement to the scheduler
-                cores = _nep_hostlu.physical_cores() if os.environ.get("NEP_HOSTLU_PIN", "1") != "0" else []
+                cores = _nep_hostlu.physical_cores() if env_str("NEP_HOSTLU_PIN", "1") != "0" else []
                 cores = cores[::-1][:max(workers, 1)] if len(cores) >= 2 * workers else []
                 cls._pool = ProcessPoolExecutor(max_workers=workers, mp_context=ctx, initializer=_nep_hostlu.pin_worker,
                                                 initargs=(ctx.Value("i", 0), cores))
@@ -126,16 +127,16 @@ class _DeviceRefactor:
     breakdown or element growth above `GROWTH` sends that matrix back to the host path."""
     plans = {}           # key -> dict(state="building"|"ready"|"off", handle, thread, strategy, fails)
     lock = threading.Lock()
-    GROWTH = float(os.environ.get("NEP_LU_DEV_GROWTH", "1e6"))
+    GROWTH = env_float("NEP_LU_DEV_GROWTH", 1e6)
     # factors whose solves are NOT followed by iterative refinement (contour_beyn's node solves; the reference pivots afresh at
     # every node): accepted only with element growth max|U| / max|A| and max|L| up to 1e3 -- the growth a threshold-pivoted
     # factorisation with diag_pivot_thresh = 1e-3 tolerates per step -- otherwise that node goes to the host
-    GROWTH_UNREFINED = float(os.environ.get("NEP_LU_DEV_GROWTH_UNREFINED", "1e3"))
+    GROWTH_UNREFINED = env_float("NEP_LU_DEV_GROWTH_UNREFINED", 1e3)
     MAX = 4
 
     @classmethod
     def enabled(cls):
-        return os.environ.get("NEP_LU_DEV", "1") != "0" and os.environ.get("NEP_LU_SCHED") != "old"
+        return env_str("NEP_LU_DEV", "1") != "0" and env_str("NEP_LU_SCHED") != "old"
 
     _digests = []          # (indptr array, indices array, digest) of the last patterns hashed: see key()
 
@@ -175,7 +176,7 @@ class _DeviceRefactor:
                 with cls.lock:
                     cls._digests.append((ip, ix, dig, fp))
                     del cls._digests[:-8]
-        knobs = tuple(os.environ.get(k) for k in ("NEP_ML_BMAX", "NEP_ML_SPLIT", "NEP_ML_CHUNK"))   # they change the partition
+        knobs = tuple(env_str(k) for k in ("NEP_ML_BMAX", "NEP_ML_SPLIT", "NEP_ML_CHUNK"))   # they change the partition
         return (dig, Ac.shape, opts, knobs)
 
     @classmethod
@@ -191,7 +192,7 @@ class _DeviceRefactor:
             return
         if not F["strategy"].get("symmetric_mode") or not np.array_equal(F["perm_r"], F["perm_c"]):
             return
-        if int(F["Lp"][-1]) + int(F["Up"][-1]) > int(os.environ.get("NEP_LU_DEV_MAXNNZ", "4000000")):
+        if int(F["Lp"][-1]) + int(F["Up"][-1]) > env_int("NEP_LU_DEV_MAXNNZ", 4000000):
             return        # factors of this size mean far more products than a plan may hold (the library would refuse it anyway)
         with cls.lock:
             if key in cls.plans:
@@ -545,7 +546,7 @@ class FactorizeLinSolver(LinSolver):
         compute_Mder on the host, no value upload, no pattern hash (1 ms of the 4.4 ms a gun linear solver took).  None: the
         caller takes the general route (no plan yet, other options, a refusal)."""
         if (permc_spec is not None or set(lu_kw) - {"expected_solves"} or not _DeviceRefactor.enabled()
-                or os.environ.get("NEP_LU_TERMS", "1") == "0"):
+                or env_str("NEP_LU_TERMS", "1") == "0"):
             return None
         from .nep import AbstractSPMF
         if not (isinstance(nep, AbstractSPMF) and type(nep).compute_Mder is AbstractSPMF.compute_Mder
@@ -643,7 +644,7 @@ class FactorizeLinSolver(LinSolver):
     def _hint(self):
         """the sweep count a previous solver of this NEP settled on AT THIS SHIFT (None otherwise): conditioning and pivot growth
         of M(sigma) change with sigma, so a count learnt at another shift says nothing about this factorisation"""
-        if os.environ.get("NEP_REFINE_HINT", "1") == "0":
+        if env_str("NEP_REFINE_HINT", "1") == "0":
             return None
         nep = getattr(self, "nep", None)
         h = getattr(nep, "_refine_hint", None)
@@ -658,8 +659,6 @@ class FactorizeLinSolver(LinSolver):
     def settled_plan(self):
         """True when the refinement count of this solver's NEP has settled (a reviewed record of this solver, or the count a
         previous solver of the NEP settled on): steps may then skip the record of the kept iterate 7 times out of 8"""
-        if os.environ.get("NEP_IAR_RECORD_ALL"):
-            return False
         if self._recorded_plan is not None:
             return True
         return self._hint() is not None
@@ -932,10 +931,10 @@ class LinSolverCache:
         device-factorisation plan they are factorised in ONE batched pass (nep_lu_factor_dev_batch: each of the ~600 launches of the
         numeric factorisation carries all of them, and their solve schedules are built together) -- config C3: five shifts, 96 -> 88 ms."""
         c = self.linsolvercreator
-        if type(c) is not FactorizeLinSolverCreator or os.environ.get("NEP_LU_PREFETCH", "1") == "0":
+        if type(c) is not FactorizeLinSolverCreator or env_str("NEP_LU_PREFETCH", "1") == "0":
             return
         if self._device_plan_ready():
-            if keep_all is not None and not getattr(self, "_batched", False) and os.environ.get("NEP_LU_CACHE_BATCH", "1") != "0":
+            if keep_all is not None and not getattr(self, "_batched", False):
                 self._batched = True
                 todo = [complex(s) for s in keep_all if np.isfinite(complex(s)) and complex(s) not in self.solvers
                         and complex(s) not in c.recycled_factorizations]
@@ -1012,9 +1011,6 @@ class LinSolverCache:
         return self._get(sigma, add_to_cache).solve_dev(y, out=out, scale=scale)
 
 
-_GMRES_TRUE_RESIDUAL = bool(os.environ.get("NEP_GMRES_TRUE_RESIDUAL"))     # A/B: re-evaluate the residual after a converged cycle
-
-
 class GMRESLinSolver(LinSolver):
     """src/LinSolvers.jl:171-188: matrix-free restarted GMRES on v -> compute_Mlincomb(nep, lam, v), i.e. every
     iteration is one K1 call (folded single-vector SpMV) + one K6 orthogonalisation (IterativeSolvers' default
@@ -1032,7 +1028,7 @@ class GMRESLinSolver(LinSolver):
         self.abstol = float(kwargs.get("abstol", 0.0))
         from . import dense as _d
         # IterativeSolvers' gmres orthogonalises with ModifiedGramSchmidt by default (orth_meth keyword)
-        self.orth = {"mgs": _d.MGS, "cgs": _d.CGS, "dgks": _d.DGKS}[str(kwargs.get("orth_meth", os.environ.get("NEP_GMRES_ORTH", "mgs"))).lower()]
+        self.orth = {"mgs": _d.MGS, "cgs": _d.CGS, "dgks": _d.DGKS}[str(kwargs.get("orth_meth", env_str("NEP_GMRES_ORTH", "mgs"))).lower()]
         Pl = kwargs.get("Pl", None)
         self._Pl_call = None
         self._Pl_inv = None
@@ -1076,7 +1072,7 @@ class GMRESLinSolver(LinSolver):
         # Givens update of column j runs on the host while the device already works on column j+1, so the only cost of the
         # convergence test is ONE speculative iteration at the end of a cycle instead of a device stall in every iteration
         # (waveguide, n = 1e6: 3300 stalls of 50-100 us per tiar run).  MGS keeps the step-synchronous loop.
-        pipelined = self.orth in (dense.DGKS, dense.CGS) and not os.environ.get("NEP_GMRES_SYNC")
+        pipelined = self.orth in (dense.DGKS, dense.CGS)
         if pipelined:
             Hdev = torch.zeros((m, m + 3), dtype=CDT, device="cuda")
             Hpin = torch.zeros((m, m + 3), dtype=CDT).pin_memory()
@@ -1143,7 +1139,7 @@ class GMRESLinSolver(LinSolver):
             y = np.linalg.solve(np.triu(H[:j_done, :j_done]), g[:j_done])
             dx = dense.gemm_ts(V, y.reshape(-1, 1), k=j_done, rows=n, ldz=n)          # (1, n)
             dense.axpy(1.0, dx, x, n)
-            if abs(g[j_done]) <= tolabs and not _GMRES_TRUE_RESIDUAL:
+            if abs(g[j_done]) <= tolabs:
                 # converged by the recurrence's residual norm: IterativeSolvers.gmres leaves here too (it evaluates the true
                 # residual only when it restarts), which saves one operator + preconditioner application per solve
                 beta = abs(g[j_done])

@@ -15,13 +15,13 @@ vector is returned and V is never modified) or such tensors (result stays on the
 """
 import ctypes as C
 
-import os
 
 import numpy as np
 import scipy.sparse as sp
 import torch
 
 from . import _lib, funcs
+from ._env import env_str
 from ._lib import lib, check, hptr, c_vp, c_i32, c_i64
 
 CDT = torch.complex128
@@ -403,7 +403,7 @@ class AbstractSPMF(NEP):
                 self.fro_norms()
             except TypeError:                 # a NEP type for which the SPMF error measure is not defined (WEP: it says so)
                 pass
-            if self.issparse() and sum(int(A.nnz) for A in self.get_Av()) <= int(os.environ.get("NEP_ALIGNED_PREFETCH_NNZ", "2000000")):
+            if self.issparse() and sum(int(A.nnz) for A in self.get_Av()) <= 2000000:      # largest sum of nnz for which the aligned term block is built with the upload
                 self._aligned_terms()
         return self._dev
 
@@ -584,7 +584,7 @@ class AbstractSPMF(NEP):
         the row-major forms at n = 1e6, but on config C5 the check as a whole did not gain (resid phase 0.180 s against 0.144 s:
         the corner term on the column-major tail goes through strided torch updates) -- the entry point is there for hosts whose
         blocks are column-major anyway (Julia)."""
-        if os.environ.get("NEP_K2_CM", "0") != "1" or self.n < 32768 or len(self.get_Av()) > 4:
+        if env_str("NEP_K2_CM", "0") != "1" or self.n < 32768 or len(self.get_Av()) > 4:
             return False
         return self.dev.tile_info()["blocks"] > 0
 

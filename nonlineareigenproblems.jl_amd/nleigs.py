@@ -21,7 +21,6 @@ the weighted block sum in between is one nep_rowdot.
 followed by K6 DGKS on the (N+1) n-row basis with per-column active row counts, and -- every check_error_every
 steps -- host `eig(K,H)`, one K7 GEMM for the Ritz block and K2 for all residuals.
 """
-import os
 import numpy as np
 import scipy.linalg as sla
 import torch
@@ -51,9 +50,9 @@ def nleigs(nep, *args, **kw):
     """src/method_nleigs.jl (see _nleigs).  The host side of a call is a few hundred small dense operations (divided differences
     of matrix functions: 102 x 102 solves, the pencil's generalised eigenproblem, Leja-Bagby points): with a threaded BLAS each of
     them pays the wake-up of the pool -- 6 ms per 102 x 102 `solve` instead of 0.3 (gun R1: 23 of 86 ms) -- so BLAS runs on one
-    thread for the duration of the call (NEP_NLEIGS_BLAS_GUARD=0: left alone), as in iar's loop."""
+    thread for the duration of the call, as in iar's loop."""
     import nep_amd_hostlu as _nep_hostlu
-    ctl = _nep_hostlu.blas_controller() if os.environ.get("NEP_NLEIGS_BLAS_GUARD", "1") != "0" else None
+    ctl = _nep_hostlu.blas_controller()
 
     def run():
         miss = False
@@ -187,8 +186,8 @@ def _nleigs(nep, Sigma=(-1.0 - 1j, -1 + 1j, 1 + 1j, 1 - 1j), Xi=(np.inf,), logge
     # is enqueued with the DGKS decision on the device (nep_orth_dev: h, beta and the flags stay in row l - 1 of Hdev) and the rows
     # are fetched in ONE copy when the pencil (K, H) is needed: at a convergence check and at the end.  The step-synchronous
     # nep_orth (h and beta read back in every step: the host waited for the device and the device for the host, 100 times per call)
-    # remains for NEP_NLEIGS_SYNC=1 and as the fallback when a step still wanted a third pass.
-    async_orth = not _sync_orth and os.environ.get("NEP_NLEIGS_SYNC", "0") == "0"
+    # remains as the fallback when a step still wanted a third pass.
+    async_orth = not _sync_orth
     if async_orth:
         Hdev = torch.zeros((ncol, ncol + 2), dtype=CDT, device="cuda")
         active_d = torch.zeros(ncol, dtype=torch.int64, device="cuda")

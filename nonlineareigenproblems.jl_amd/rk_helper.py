@@ -6,6 +6,7 @@ import numpy as np
 
 import scipy.sparse as sp
 
+from ._env import env_str
 from .nep import PEP, SumNEP, LowRankFactorizedNEP
 
 
@@ -48,8 +49,7 @@ def in_Sigma(z, Sigma, tol):
 
 def _discretize_native(zv, L, npts):
     """the boundary walk through the library (host code); None when switched off or not applicable"""
-    import os
-    if os.environ.get("NEP_RK_NATIVE", "1") == "0" or npts < 1 or len(zv) < 3 or not np.isfinite(L) or not L > 0:
+    if env_str("NEP_RK_NATIVE", "1") == "0" or npts < 1 or len(zv) < 3 or not np.isfinite(L) or not L > 0:
         return None
     from ._lib import lib, hptr
     zc = np.ascontiguousarray(zv, dtype=np.complex128)

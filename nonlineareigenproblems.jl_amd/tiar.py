@@ -13,7 +13,6 @@ Reference step (method_tiar.jl:116-239)               device realisation
   VV=Z[:,1:k]*transpose(a[1,1:k,1:k]); Q=VV*W              ONE K7 GEMM with the k x k product formed on the host
   err[k,s]=estimate_error(...)                             K2 nep_resid_batch
 """
-import os
 import time
 
 import numpy as np
@@ -80,8 +79,8 @@ def tiar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
     # of H exists (LAPACK runs without the GIL), Ritz block + residual batch of all steps are issued back to back behind the
     # recurrence with the host preparing check k + 1 while the device works on check k.  Same arithmetic, same history, same
     # results; the recurrence no longer waits twice per step for a host eigen-decomposition and two read-backs (config C5:
-    # 60 steps x ~2.5 ms).  Instrumented runs (timers), proj_solve and NEP_TIAR_DEFER=0 keep the step-synchronous order.
-    defer = bool(np.isinf(neigs)) and timers is None and not proj_solve and os.environ.get("NEP_TIAR_DEFER", "1") != "0"
+    # 60 steps x ~2.5 ms).  Instrumented runs (timers) and proj_solve keep the step-synchronous order.
+    defer = bool(np.isinf(neigs)) and timers is None and not proj_solve
     deferred = []
     eig_pool = None
     if defer:

@@ -10,7 +10,6 @@ rank-one nz x nz blocks (2 nz^3 = 2e9 non-zeros at nz = 999).  Here the NEP is
 i.e. three big REAL sparse matrices in one stacked CSR (the HBM-bound part) plus a factored corner term applied as
 two small dense products with Rm (nz x nz, the scaled DFT matrix of Waveguide.jl:53-65).
 """
-import os
 
 import numpy as np
 import scipy.sparse as sp
@@ -121,6 +120,7 @@ class WaveguideData:
 import torch
 
 from . import _lib
+from ._env import env_str
 from ._lib import lib, check, hptr, c_vp
 from .nep import AbstractSPMF, CDT, to_dev, to_host, is_dev, stream_ptr
 
@@ -182,18 +182,16 @@ class WEP(AbstractSPMF):
 
     # ---- corner data on the device
     def _pinv_plan(self):
-        """nep_wep_pinv handle (prime-factor DFT plan + bb on the device) for P(lam)^{-1}, or None (NEP_WEP_GEMM=1 / nz too large:
+        """nep_wep_pinv handle (prime-factor DFT plan + bb on the device) for P(lam)^{-1}, or None (nz too large:
         the dense R matrices are used instead)"""
         if getattr(self, "_pinv_h", False) is False:
             self._pinv_h = None
-            import os
-            if not os.environ.get("NEP_WEP_GEMM"):
-                import ctypes as C
-                _lib.require_gpu()
-                h = c_vp()
-                bb = np.ascontiguousarray(self.wd.bb, dtype=np.complex128)
-                if lib.nep_wep_pinv_create(self.nz, hptr(bb), C.byref(h)) == 0:
-                    self._pinv_h = h
+            import ctypes as C
+            _lib.require_gpu()
+            h = c_vp()
+            bb = np.ascontiguousarray(self.wd.bb, dtype=np.complex128)
+            if lib.nep_wep_pinv_create(self.nz, hptr(bb), C.byref(h)) == 0:
+                self._pinv_h = h
         return self._pinv_h
 
     def _corner_dev(self):
@@ -305,7 +303,7 @@ class WEP(AbstractSPMF):
         """enqueues the residual batch and the corner term; the returned object's get() runs the two synchronising read-backs
         (tiar's deferred convergence checks: the host prepares check k + 1 while the device works on check k)"""
         from .nep import PendingNorms
-        if hasattr(QT, "cpu_matrix") or os.environ.get("NEP_WEP_RESID_SPLIT", "1") == "0":
+        if hasattr(QT, "cpu_matrix") or env_str("NEP_WEP_RESID_SPLIT", "1") == "0":
             return PendingNorms(result=self.resid_norms(lams, QT))
         fin = self.resid_norms(lams, QT, _defer=True)
         ev = torch.cuda.Event(); ev.record()
@@ -357,7 +355,7 @@ class WEP(AbstractSPMF):
             o = out.cpu().numpy()
             return np.sqrt(o[:k] + tn2.cpu().numpy()), np.sqrt(o[k:]), F
         ldq = QT.shape[1]
-        split = os.environ.get("NEP_WEP_RESID_SPLIT", "1") != "0"
+        split = env_str("NEP_WEP_RESID_SPLIT", "1") != "0"
         if split:
             out = torch.zeros(2 * k, dtype=torch.float64, device="cuda")
             RT = torch.empty((2 * nz, k), dtype=CDT, device="cuda")                 # residual rows N .. n-1 only

@@ -19,13 +19,13 @@ region sums / expansions of the SMW correction are products with 0/1 indicator m
 matrix is inverted once on the host and applied as a GEMV, so one preconditioner application never synchronises.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import scipy.sparse as sp
 import torch
 
 from . import _lib, dense
+from ._env import env_str
 from ._lib import lib, check, c_vp
 from .linsolvers import DeviceLU, FactorizeLinSolver, GMRESLinSolver, LinSolver, LinSolverCreator
 from .nep import CDT, DeviceCSR, to_dev, to_host, is_dev, stream_ptr
@@ -70,7 +70,7 @@ class SchurOps:
         # generate_fd_interior_mat / generate_fd_boundary_mat (Waveguide.jl:17-19), diagonal K + lam^2 - 2/hz^2 - 2/hx^2
         wd = nep.wd
         self.stencil = None
-        if nep._pinv_plan() is not None and os.environ.get("NEP_WEP_STENCIL", "1") != "0":
+        if nep._pinv_plan() is not None and env_str("NEP_WEP_STENCIL", "1") != "0":
             lam_ = self.lam
             D0 = np.asarray(wd.K, dtype=np.complex128) + (lam_ ** 2 - 2.0 / wd.hz ** 2 - 2.0 / wd.hx ** 2)
             self.stencil = dict(D0=to_dev(D0), cp=_lib.cd(1.0 / wd.hz ** 2 + lam_ / wd.hz), cm=_lib.cd(1.0 / wd.hz ** 2 - lam_ / wd.hz),
@@ -255,7 +255,7 @@ class WEPGMRESLinSolver(LinSolver):
         # the graph remains for the piecewise routes (~30 launches from Python per step)
         Pl = self.gmres._Pl_call
         direct = self.ops.stencil is not None and isinstance(Pl, WEPPreconditioner) and Pl.fused_available()
-        if Pl is not None and os.environ.get("NEP_WEP_GRAPH", "0" if direct else "1") != "0":
+        if Pl is not None and not direct:
             self._capture_step()
         elif direct:
             # straight from basis vector j into basis vector j + 1: no operator-owned output block and no copy behind it
@@ -362,18 +362,16 @@ class WEPPreconditioner:
         D = np.fft.fft(v + w) + (self.sigma ** 2 + k_bar)
         # Sylvester solve: prime-factor DFT along z + one tridiagonal solve per z-mode along x (csrc/wep.hip); the dense
         # transform matrices of round 1 (dense GEMMs, since round 3 the library's own k_gemm_general) serve the shapes those
-        # kernels do not take (nx > 2048) and remain the A/B reference behind NEP_WEP_GEMM=1
+        # kernels do not take (nx > 2048)
         self.sylv = None
         self.dd1 = (2 / wd.hx) / wd.hx ** 2; self.dd2 = (-1 / (2 * wd.hx)) / wd.hx ** 2
-        if not os.environ.get("NEP_WEP_GEMM"):
-            import ctypes as C
-            h = c_vp()
-            Dc = np.ascontiguousarray(D, dtype=np.complex128)
-            st = lib.nep_wep_sylv_create(nz, nx, _lib.hptr(Dc), 1.0 / wd.hx ** 2, C.byref(h))
-            if st == 0:
-                self.sylv = h
-            elif st != _lib.NEP_ERR_UNSUPPORTED:
-                check(st)
+        h = c_vp()
+        Dc = np.ascontiguousarray(D, dtype=np.complex128)
+        st = lib.nep_wep_sylv_create(nz, nx, _lib.hptr(Dc), 1.0 / wd.hx ** 2, C.byref(h))
+        if st == 0:
+            self.sylv = h
+        elif st != _lib.NEP_ERR_UNSUPPORTED:
+            check(st)
         if self.sylv is None:
             S = -(4.0 / wd.hx ** 2) * np.sin(np.pi * np.arange(1, nx + 1) / (2 * (nx + 1))) ** 2
             self.G = to_dev(1.0 / (D[:, None] + S[None, :]))                                   # nz x nx
@@ -404,7 +402,7 @@ class WEPPreconditioner:
         self.pb = e(2 * nz)
         self.MinvH = None
         self._G = None
-        self._fused = False if os.environ.get("NEP_WEP_SMW_FUSED", "1") == "0" else None     # None: not tried yet
+        self._fused = False if env_str("NEP_WEP_SMW_FUSED", "1") == "0" else None     # None: not tried yet
         self._generate()
 
     def __del__(self):
@@ -499,17 +497,16 @@ class WEPPreconditioner:
     def _set_inverse(self, Mdev, mm):
         """MinvH = inv(I + M)^H (alpha = (MinvH)^H f through nep_gemv_hd).  On the device by the library's Gauss-Jordan inverse
         (nep_zinv_h_dev: 2 launches per column; 1517 x 1517 in ~35 ms against 0.14 s of numpy.linalg.inv on 8 BLAS threads + two
-        36 MB transfers); NEP_WEP_SMW_INV=host keeps the host route, which is also the fallback for a zero pivot."""
+        36 MB transfers); the host route is the fallback for a zero pivot."""
         self._Mdev = Mdev
         self._M_host = None
-        if os.environ.get("NEP_WEP_SMW_INV", "dev") != "host":
-            out = torch.empty((mm, mm), dtype=CDT, device="cuda")
-            work = torch.empty(2 * mm + 2, dtype=CDT, device="cuda")
-            info = C.c_int32(0)
-            check(lib.nep_zinv_h_dev(mm, _p(Mdev), mm, 1.0, _p(out), mm, _p(work), C.byref(info), stream_ptr()))
-            if info.value == 0:
-                self.MinvH = out
-                return
+        out = torch.empty((mm, mm), dtype=CDT, device="cuda")
+        work = torch.empty(2 * mm + 2, dtype=CDT, device="cuda")
+        info = C.c_int32(0)
+        check(lib.nep_zinv_h_dev(mm, _p(Mdev), mm, 1.0, _p(out), mm, _p(work), C.byref(info), stream_ptr()))
+        if info.value == 0:
+            self.MinvH = out
+            return
         self._M_host = to_host(Mdev) + np.eye(mm)
         self.MinvH = to_dev(np.linalg.inv(self._M_host).conj().T)
 
