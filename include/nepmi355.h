@@ -502,8 +502,30 @@ int32_t nep_rowmajor_to_colmajor(int64_t rows, int32_t k, const nep_cdouble* dsr
 typedef struct nep_wep_sylv nep_wep_sylv;
 int32_t nep_wep_sylv_create(int32_t nz, int32_t nx, const nep_cdouble* h_d, double b, nep_wep_sylv** out);
 int32_t nep_wep_sylv_destroy(nep_wep_sylv* s);
-int32_t nep_wep_sylv_info(const nep_wep_sylv* s, int32_t out[4]);   /* N1, N2 (nz = N1 N2 coprime), columns per workgroup, x per lane */
+int32_t nep_wep_sylv_info(const nep_wep_sylv* s, int32_t out[4]);   /* N1, N2 (nz = N1 N2 coprime), columns per workgroup, SEG of k_tridiag_modes (x per lane) */
 int32_t nep_wep_sylv_solve(nep_wep_sylv* s, nep_cdouble* dX, nep_stream stream);
+/* Dispatch query of the waveguide kernels: which instantiation the entry points named by `op` launch on an nz x nx grid.  Host
+ * only: touches no device, launches nothing; it evaluates the very functions the launchers call (tests assert with it that
+ * their cases reach the instantiation they are named for).
+ *   op = NEP_WEP_PLAN_SYLV  nep_wep_sylv_create / nep_wep_sylv_solve
+ *        NEP_WEP_PLAN_PINV  nep_wep_pinv_create / nep_wep_pinv_apply and the boundary half of nep_wep_schur_matvec (nx ignored)
+ *        NEP_WEP_PLAN_SMW   nep_wep_smw_apply / nep_wep_smw_matrix_modes
+ *   info[0], info[1] N1, N2 (nz = N1 N2 coprime, smallest N1 + N2)
+ *   info[2] NEP_WEP_PLAN_K_RB | _PLAIN | _SYM: k_dft_cols_rb, k_dft_cols, k_dft_cols_sym (SYLV, SMW); k_wep_pinv, k_wep_pinv_sym (PINV)
+ *   info[3] grid columns per workgroup (PINV: 1)      info[4] outputs per thread of a dense stage (KB)
+ *   info[5] threads per workgroup                     info[6] dynamic LDS bytes of that kernel; SMW: of the row buffer of
+ *                                                             k_tridiag_modes<SEG, 1> (the transform is the one SYLV reports)
+ *   info[7] SEG of k_tridiag_modes (PINV: 0)
+ * NEP_ERR_UNSUPPORTED (info all zero) exactly where the entry point refuses: nz beyond the LDS staging of the transform (SYLV,
+ * SMW) or of P^{-1} (PINV, SMW); SMW without the symmetric-half form or with a row buffer above 150 KiB.
+ * NEP_ERR_ARG: info NULL, unknown op, nz < 1; SYLV and SMW: nx < 2 or nx > 2048; SMW: nx != nz + 4. */
+#define NEP_WEP_PLAN_SYLV 0
+#define NEP_WEP_PLAN_PINV 1
+#define NEP_WEP_PLAN_SMW 2
+#define NEP_WEP_PLAN_K_RB 1
+#define NEP_WEP_PLAN_K_PLAIN 2
+#define NEP_WEP_PLAN_K_SYM 3
+int32_t nep_wep_plan(int32_t nz, int32_t nx, int32_t op, int64_t info[8]);
 /* boundary operator of the waveguide: dOut (2 nz) = blkdiag(R, R) diag(d_sinv) blkdiag(R, R)^H dX with R x = reverse(bb .* fft(x))
  * (Waveguide.jl:53-65) and d_sinv = 1 / (nz s_j(lam)) (P_inv_m / P_inv_p, Waveguide.jl:159-170): two prime-factor DFTs per half
  * in ONE launch (replaces four dense nz x nz GEMVs).  dOut may alias dX. */

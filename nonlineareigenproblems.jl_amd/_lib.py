@@ -141,6 +141,7 @@ SIGNATURES = {
     "nep_wep_sylv_destroy": [c_vp],
     "nep_wep_sylv_info": [c_vp, P(c_i32)],
     "nep_wep_sylv_solve": [c_vp, c_vp, c_vp],
+    "nep_wep_plan": [c_i32, c_i32, c_i32, P(c_i64)],
     "nep_wep_pinv_create": [c_i32, c_vp, P(c_vp)],
     "nep_wep_pinv_destroy": [c_vp],
     "nep_wep_pinv_apply": [c_vp, c_vp, c_vp, c_vp, c_vp],

@@ -851,6 +851,70 @@ static int egcd_inv(int a, int m) {            // a^{-1} mod m (gcd = 1)
     return t < 0 ? t + m : t;
 }
 
+// ---- launch choices, each stated once: the launchers below and nep_wep_plan evaluate these same functions ------------------------
+static const size_t WEP_LDS_MAX = 150 * 1024;
+// coprime factorisation nz = N1 N2 with the smallest N1 + N2 (N2 = 1: plain dense DFT of length nz)
+static void wep_factor(int nz, int& N1, int& N2) {
+    N1 = nz; N2 = 1;
+    for (int a = 2; a * a <= nz; ++a)
+        if (nz % a == 0 && std::gcd(a, nz / a) == 1 && a + nz / a < N1 + N2) { N1 = nz / a; N2 = a; }
+}
+// dynamic LDS of k_dft_cols / k_dft_cols_rb (two staging buffers of `cols` columns) and of k_dft_cols_sym (one)
+static size_t wep_dft_shm(int bufs, int cols, int nz, int N1, int N2) { return ((size_t)bufs * cols * nz + N1 + N2) * sizeof(cplx); }
+// columns per workgroup of the plain / register-blocked DFT: 4 while they fit the LDS, else 2, else 1; 0: not even one column fits
+static int wep_dft_cols(int nz, int N1, int N2) {
+    int cols = 4;
+    while (cols > 1 && wep_dft_shm(2, cols, nz, N1, N2) > WEP_LDS_MAX) cols >>= 1;
+    return wep_dft_shm(2, cols, nz, N1, N2) > WEP_LDS_MAX ? 0 : cols;
+}
+// threads per workgroup of k_dft_cols_rb (cols = 4) / k_dft_cols<*, cols>
+static int wep_dft_threads(int nz, int cols) { return cols == 4 ? 384 : (nz >= 768 ? 1024 : (nz >= 384 ? 512 : 256)); }
+// SEG of k_tridiag_modes: the smallest power of two with 64 SEG >= nx (nx <= 2048: at most 32)
+static int wep_seg(int nx) {
+    int seg = 1;
+    while (64 * seg < nx) seg <<= 1;
+    return seg;
+}
+// dynamic LDS of k_tridiag_modes<*, 1>: the solutions of the four modes of a workgroup in plain x order
+static size_t wep_rowbuf_shm(int nx) { return (size_t)4 * nx * sizeof(cplx); }
+// symmetric-half form of the two dense stages (odd N1, N2): NEP_WEP_DFT_SYM = "cols*10 + kb" (42, 43, 22, 23) or 0 = off
+static int wep_dft_sym_env() {
+    static const int symcfg = nep_env_int("NEP_WEP_DFT_SYM", 22);
+    return symcfg;
+}
+struct SymCfg { int cols = 0, kb = 0, threads = 0; size_t shm = 0; unsigned grid = 0; };
+static bool wep_sym_cfg(int nz, int nx, int N1, int N2, SymCfg& c) {
+    const int symcfg = wep_dft_sym_env();
+    c.cols = symcfg / 10; c.kb = symcfg % 10;
+    if (!(symcfg && (N1 & 1) && (N2 & 1) && N1 >= 3 && N2 >= 3 && (c.cols == 2 || c.cols == 4) && (c.kb == 2 || c.kb == 3)))
+        return false;
+    const int H1 = (N1 - 1) / 2, H2 = (N2 - 1) / 2;
+    const int items = std::max(((H1 + c.kb - 1) / c.kb) * N2, ((H2 + c.kb - 1) / c.kb) * N1);
+    c.threads = (items + 63) / 64 * 64;
+    c.shm = wep_dft_shm(1, c.cols, nz, N1, N2);
+    if (c.threads > 512 || c.shm > WEP_LDS_MAX) return false;
+    c.grid = (unsigned)((nx + c.cols - 1) / c.cols);
+    return true;
+}
+static bool sylv_sym_cfg(const nep_wep_sylv* s, SymCfg& c) { return wep_sym_cfg(s->nz, s->nx, s->N1, s->N2, c); }
+// the three-transform SMW forms need the symmetric-half DFT and the row buffer of k_tridiag_modes<*, 1> in LDS
+static bool wep_smw_cfg(int nz, int nx, int N1, int N2, SymCfg& c) {
+    return wep_sym_cfg(nz, nx, N1, N2, c) && wep_rowbuf_shm(nx) <= WEP_LDS_MAX;
+}
+// P(lam)^{-1}: does nz fit the LDS staging at all, and which kernel takes it (k_wep_pinv_sym while its work items fit 512 threads)
+static bool wep_pinv_fits(int nz) { return ((size_t)3 * nz + 2 * (size_t)nz) * sizeof(cplx) <= WEP_LDS_MAX; }
+struct PinvCfg { bool sym = false; int threads = 0; size_t shm = 0; };
+static PinvCfg wep_pinv_cfg(int nz, int N1, int N2) {
+    PinvCfg c;
+    if ((N1 & 1) && (N2 & 1) && N1 >= 3 && N2 >= 3) {
+        const int items = std::max((N1 - 1) / 2 * N2, (N2 - 1) / 2 * N1);
+        if (items <= 512) { c.sym = true; c.threads = (items + 63) / 64 * 64; c.shm = ((size_t)2 * nz + N1 + N2) * sizeof(cplx); return c; }
+    }
+    c.threads = nz >= 768 ? 1024 : (nz >= 256 ? 512 : 256);
+    c.shm = ((size_t)3 * nz + N1 + N2) * sizeof(cplx);
+    return c;
+}
+
 extern "C" {
 
 int32_t nep_wep_sylv_destroy(nep_wep_sylv* s) {
@@ -865,13 +929,10 @@ int32_t nep_wep_sylv_create(int32_t nz, int32_t nx, const nep_cdouble* h_d, doub
     ARGCHK(out != nullptr);
     *out = nullptr;
     ARGCHK(nz >= 1 && nx >= 2 && h_d != nullptr && nx <= 64 * 32);
-    // coprime factorisation with the smallest N1 + N2 (N2 = 1: plain dense DFT of length nz)
-    int N1 = nz, N2 = 1;
-    for (int a = 2; a * a <= nz; ++a)
-        if (nz % a == 0 && std::gcd(a, nz / a) == 1 && a + nz / a < N1 + N2) { N1 = nz / a; N2 = a; }
-    int cols = 4;          // columns per workgroup: 4 while they fit the LDS, else 2, else 1
-    while (cols > 1 && ((size_t)2 * cols * nz + N1 + N2) * sizeof(cplx) > 150 * 1024) cols >>= 1;
-    if (((size_t)2 * cols * nz + N1 + N2) * sizeof(cplx) > 150 * 1024) {
+    int N1, N2;
+    wep_factor(nz, N1, N2);
+    const int cols = wep_dft_cols(nz, N1, N2);
+    if (!cols) {
         nep_set_error("nep_wep_sylv_create: nz = %d does not fit the LDS staging of the DFT kernel", nz);
         return NEP_ERR_UNSUPPORTED;
     }
@@ -888,9 +949,10 @@ int32_t nep_wep_sylv_create(int32_t nz, int32_t nx, const nep_cdouble* h_d, doub
     std::vector<nep_cdouble> w1(N1), w2(N2);
     for (int j = 0; j < N1; ++j) { const double th = -2.0 * M_PI * j / N1; w1[j].re = cos(th); w1[j].im = sin(th); }
     for (int j = 0; j < N2; ++j) { const double th = -2.0 * M_PI * j / N2; w2[j].re = cos(th); w2[j].im = sin(th); }
-    {   // SEG of k_tridiag_modes (nep_wep_sylv_solve): the smallest power of two with 64 SEG >= nx
-        int seg = 1, lseg = 0;
-        while (64 * seg < nx) { seg <<= 1; ++lseg; }
+    {   // SEG of k_tridiag_modes (nep_wep_sylv_solve) decides the layout of the transposed blocks
+        const int seg = wep_seg(nx);
+        int lseg = 0;
+        while ((1 << lseg) < seg) ++lseg;
         s->lseg = lseg; s->ldt = seg >= 4 ? 64 * seg : nx;
     }
     const size_t ldt = (size_t)s->ldt;
@@ -938,10 +1000,9 @@ int32_t nep_wep_pinv_create(int32_t nz, const nep_cdouble* h_bb, nep_wep_pinv** 
     ARGCHK(out != nullptr);
     *out = nullptr;
     ARGCHK(nz >= 1 && h_bb != nullptr);
-    if (((size_t)3 * nz + 2 * (size_t)nz) * sizeof(cplx) > 150 * 1024) { nep_set_error("nep_wep_pinv_create: nz = %d too large for the LDS staging", nz); return NEP_ERR_UNSUPPORTED; }
-    int N1 = nz, N2 = 1;
-    for (int a = 2; a * a <= nz; ++a)
-        if (nz % a == 0 && std::gcd(a, nz / a) == 1 && a + nz / a < N1 + N2) { N1 = nz / a; N2 = a; }
+    if (!wep_pinv_fits(nz)) { nep_set_error("nep_wep_pinv_create: nz = %d too large for the LDS staging", nz); return NEP_ERR_UNSUPPORTED; }
+    int N1, N2;
+    wep_factor(nz, N1, N2);
     nep_wep_pinv* p = new nep_wep_pinv();
     p->nz = nz; p->N1 = N1; p->N2 = N2;
     std::vector<int32_t> in_idx(nz), out_idx(nz);
@@ -982,19 +1043,15 @@ static int32_t pinv_apply_impl(nep_wep_pinv* p, const nep_cdouble* d_sinv, const
                                const cplx* gX, int gnx, double gd1, double gd2) {
     static thread_local bool attr_set = false;
     if (!attr_set) { HIPCHK(hipFuncSetAttribute((const void*)k_wep_pinv, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); attr_set = true; }
-    if ((p->N1 & 1) && (p->N2 & 1) && p->N1 >= 3 && p->N2 >= 3) {
-        const int items = std::max((p->N1 - 1) / 2 * p->N2, (p->N2 - 1) / 2 * p->N1);
-        if (items <= 512) {
-            hipLaunchKernelGGL(k_wep_pinv_sym, dim3(2), dim3((items + 63) / 64 * 64), ((size_t)2 * p->nz + p->N1 + p->N2) * sizeof(cplx),
-                               as_stream(stream), p->nz, p->N1, p->N2, (const int32_t*)p->d_in, (const int32_t*)p->d_out, (const cplx*)p->d_w1,
-                               (const cplx*)p->d_w2, (const cplx*)p->d_bb, (const cplx*)d_sinv, (const cplx*)dX, (cplx*)dOut, gX, gnx, gd1, gd2);
-            LAUNCHCHK();
-            return NEP_OK;
-        }
+    const PinvCfg c = wep_pinv_cfg(p->nz, p->N1, p->N2);
+    if (c.sym) {
+        hipLaunchKernelGGL(k_wep_pinv_sym, dim3(2), dim3(c.threads), c.shm,
+                           as_stream(stream), p->nz, p->N1, p->N2, (const int32_t*)p->d_in, (const int32_t*)p->d_out, (const cplx*)p->d_w1,
+                           (const cplx*)p->d_w2, (const cplx*)p->d_bb, (const cplx*)d_sinv, (const cplx*)dX, (cplx*)dOut, gX, gnx, gd1, gd2);
+        LAUNCHCHK();
+        return NEP_OK;
     }
-    const size_t shm = ((size_t)3 * p->nz + p->N1 + p->N2) * sizeof(cplx);
-    const int threads = p->nz >= 768 ? 1024 : (p->nz >= 256 ? 512 : 256);
-    hipLaunchKernelGGL(k_wep_pinv, dim3(2), dim3(threads), shm, as_stream(stream), p->nz, p->N1, p->N2, (const int32_t*)p->d_in,
+    hipLaunchKernelGGL(k_wep_pinv, dim3(2), dim3(c.threads), c.shm, as_stream(stream), p->nz, p->N1, p->N2, (const int32_t*)p->d_in,
                        (const int32_t*)p->d_out, (const cplx*)p->d_w1, (const cplx*)p->d_w2, (const cplx*)p->d_bb, (const cplx*)d_sinv,
                        (const cplx*)dX, (cplx*)dOut, gX, gnx, gd1, gd2);
     LAUNCHCHK();
@@ -1042,7 +1099,46 @@ int32_t nep_wep_schur_matvec(nep_wep_pinv* p, const nep_cdouble* d_sinv, int32_t
 
 int32_t nep_wep_sylv_info(const nep_wep_sylv* s, int32_t out[4]) {
     ARGCHK(s && out);
-    out[0] = s->N1; out[1] = s->N2; out[2] = s->cols; out[3] = (s->nx + 63) / 64;
+    out[0] = s->N1; out[1] = s->N2; out[2] = s->cols; out[3] = wep_seg(s->nx);
+    return NEP_OK;
+}
+
+// dispatch query (include/nepmi355.h): the launch choices of the entry points of this file, reported instead of launched.  Host only.
+// serves: solve_wg_sylvester_fft! waveguide_preconditioner.jl:120-219 (NEP_WEP_PLAN_SYLV), P_inv_m / P_inv_p Waveguide.jl:159-170
+//         (NEP_WEP_PLAN_PINV), solve_smw / generate_smw_matrix waveguide_preconditioner.jl:221-421 (NEP_WEP_PLAN_SMW)
+int32_t nep_wep_plan(int32_t nz, int32_t nx, int32_t op, int64_t info[8]) {
+    ARGCHK(info != nullptr);
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    ARGCHK(op == NEP_WEP_PLAN_SYLV || op == NEP_WEP_PLAN_PINV || op == NEP_WEP_PLAN_SMW);
+    ARGCHK(nz >= 1);
+    int N1, N2;
+    wep_factor(nz, N1, N2);
+    int64_t kernel, cols, kb, threads, shm, seg = 0;
+    if (op == NEP_WEP_PLAN_PINV) {
+        if (!wep_pinv_fits(nz)) { nep_set_error("nep_wep_plan: nz = %d too large for the LDS staging of P^{-1}", nz); return NEP_ERR_UNSUPPORTED; }
+        const PinvCfg c = wep_pinv_cfg(nz, N1, N2);
+        kernel = c.sym ? NEP_WEP_PLAN_K_SYM : NEP_WEP_PLAN_K_PLAIN; cols = 1; kb = 1; threads = c.threads; shm = (int64_t)c.shm;
+    } else {
+        ARGCHK(nx >= 2 && nx <= 64 * 32);                              // nep_wep_sylv_create
+        ARGCHK(op != NEP_WEP_PLAN_SMW || nx == nz + 4);                // nep_wep_smw_apply, nep_wep_smw_matrix_modes
+        const int pc = wep_dft_cols(nz, N1, N2);
+        if (!pc) { nep_set_error("nep_wep_plan: nz = %d does not fit the LDS staging of the DFT kernel", nz); return NEP_ERR_UNSUPPORTED; }
+        SymCfg c;
+        seg = wep_seg(nx);
+        if (op == NEP_WEP_PLAN_SMW) {
+            if (!wep_pinv_fits(nz) || !wep_smw_cfg(nz, nx, N1, N2, c)) {
+                nep_set_error("nep_wep_plan: no three-transform SMW form for nz = %d", nz);
+                return NEP_ERR_UNSUPPORTED;
+            }
+            kernel = NEP_WEP_PLAN_K_SYM; cols = c.cols; kb = c.kb; threads = c.threads; shm = (int64_t)wep_rowbuf_shm(nx);
+        } else if (wep_sym_cfg(nz, nx, N1, N2, c)) {
+            kernel = NEP_WEP_PLAN_K_SYM; cols = c.cols; kb = c.kb; threads = c.threads; shm = (int64_t)c.shm;
+        } else {
+            kernel = pc == 4 ? NEP_WEP_PLAN_K_RB : NEP_WEP_PLAN_K_PLAIN; cols = pc; kb = pc == 4 ? 3 : 1;
+            threads = wep_dft_threads(nz, pc); shm = (int64_t)wep_dft_shm(2, pc, nz, N1, N2);
+        }
+    }
+    info[0] = N1; info[1] = N2; info[2] = kernel; info[3] = cols; info[4] = kb; info[5] = threads; info[6] = shm; info[7] = seg;
     return NEP_OK;
 }
 
@@ -1051,7 +1147,7 @@ int32_t nep_wep_sylv_solve(nep_wep_sylv* s, nep_cdouble* dX, nep_stream stream) 
     ARGCHK(s && dX);
     hipStream_t st = as_stream(stream);
     const int nz = s->nz, nx = s->nx;
-    const size_t shm = ((size_t)2 * s->cols * nz + s->N1 + s->N2) * sizeof(cplx);
+    const size_t shm = wep_dft_shm(2, s->cols, nz, s->N1, s->N2);
     static thread_local bool attr_set = false;
     if (!attr_set) {
 #define DFT_ATTR(F_, C_) HIPCHK(hipFuncSetAttribute((const void*)k_dft_cols<F_, C_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024))
@@ -1064,26 +1160,21 @@ int32_t nep_wep_sylv_solve(nep_wep_sylv* s, nep_cdouble* dX, nep_stream stream) 
     const double scale = 1.0 / sqrt((double)nz);
     const TLay tl{s->ldt, s->lseg};
     const dim3 grid((unsigned)((nx + s->cols - 1) / s->cols));
-    const int threads = nz >= 768 ? 1024 : (nz >= 384 ? 512 : 256);
+    const int threads = wep_dft_threads(nz, s->cols);
 #define DFT_LAUNCH(F_, C_, SGN_, SRC_, DST_)                                                                               \
     hipLaunchKernelGGL((k_dft_cols<F_, C_>), grid, dim3(threads), shm, st, nz, nx, s->N1, s->N2, (const int32_t*)s->d_in,    \
                        (const int32_t*)s->d_out, (const cplx*)s->d_w1, (const cplx*)s->d_w2, SGN_, scale, SRC_, DST_, xcd_order, tl)
     const int xcd_order = WEP_DFT_XCD_ORDER;
 #define DFT_BY_COLS(F_, SGN_, SRC_, DST_)                                                                                  \
     do { if (s->cols == 4)                                                                                                  \
-             hipLaunchKernelGGL((k_dft_cols_rb<F_>), grid, dim3(384), shm, st, nz, nx, s->N1, s->N2, (const int32_t*)s->d_in, \
+             hipLaunchKernelGGL((k_dft_cols_rb<F_>), grid, dim3(threads), shm, st, nz, nx, s->N1, s->N2, (const int32_t*)s->d_in, \
                                 (const int32_t*)s->d_in_inv, (const int32_t*)s->d_out, (const cplx*)s->d_w1, (const cplx*)s->d_w2, SGN_, scale, SRC_, DST_, xcd_order, tl); \
          else if (s->cols == 2) DFT_LAUNCH(F_, 2, SGN_, SRC_, DST_);                                                         \
          else DFT_LAUNCH(F_, 1, SGN_, SRC_, DST_); } while (0)
-    // symmetric-half form of the two dense stages (odd N1, N2): NEP_WEP_DFT_SYM = "cols*10 + kb" (42, 43, 22, 23) or 0 = off
-    static const int symcfg = nep_env_int("NEP_WEP_DFT_SYM", 22);
-    int sym_cols = symcfg / 10, sym_kb = symcfg % 10, sym_threads = 0;
-    if (symcfg && (s->N1 & 1) && (s->N2 & 1) && s->N1 >= 3 && s->N2 >= 3 && (sym_cols == 2 || sym_cols == 4) && (sym_kb == 2 || sym_kb == 3)) {
-        const int H1 = (s->N1 - 1) / 2, H2 = (s->N2 - 1) / 2;
-        const int items = std::max(((H1 + sym_kb - 1) / sym_kb) * s->N2, ((H2 + sym_kb - 1) / sym_kb) * s->N1);
-        sym_threads = (items + 63) / 64 * 64;
-        if (sym_threads > 512 || ((size_t)sym_cols * nz + s->N1 + s->N2) * sizeof(cplx) > 150 * 1024) sym_threads = 0;
-    }
+    // symmetric-half form of the two dense stages where sylv_sym_cfg grants it
+    SymCfg sc;
+    const int sym_threads = sylv_sym_cfg(s, sc) ? sc.threads : 0;
+    const int sym_cols = sc.cols, sym_kb = sc.kb;
     if (sym_threads) {
         static thread_local bool sym_attr = false;
         if (!sym_attr) {
@@ -1094,8 +1185,8 @@ int32_t nep_wep_sylv_solve(nep_wep_sylv* s, nep_cdouble* dX, nep_stream stream) 
             sym_attr = true;
         }
     }
-    const size_t sym_shm = ((size_t)sym_cols * nz + s->N1 + s->N2) * sizeof(cplx);
-    const dim3 sym_grid((unsigned)((nx + std::max(sym_cols, 1) - 1) / std::max(sym_cols, 1)));
+    const size_t sym_shm = sc.shm;
+    const dim3 sym_grid(sc.grid);
 #define SYM_LAUNCH(F_, C_, K_, SGN_, SRC_, DST_)                                                                             \
     hipLaunchKernelGGL((k_dft_cols_sym<F_, C_, K_>), sym_grid, dim3(sym_threads), sym_shm, st, nz, nx, s->N1, s->N2,          \
                        (const int32_t*)s->d_in, (const int32_t*)s->d_in_inv, (const int32_t*)s->d_out, (const cplx*)s->d_w1,  \
@@ -1109,10 +1200,10 @@ int32_t nep_wep_sylv_solve(nep_wep_sylv* s, nep_cdouble* dX, nep_stream stream) 
     if (sym_threads) DFT_SYM(true, -1.0, (const cplx*)dX, s->d_T);
     else DFT_BY_COLS(true, -1.0, (const cplx*)dX, s->d_T);
     LAUNCHCHK();
-    const int seg = (nx + 63) / 64;
+    const int seg = wep_seg(nx);
     const dim3 g2((unsigned)((nz + 3) / 4));
 #define TRI(S_) hipLaunchKernelGGL((k_tridiag_modes<S_, 0>), g2, dim3(256), 0, st, nz, nx, (const cplx*)s->d_m, (const cplx*)s->d_dinv, s->b, s->d_T)
-    if (seg <= 1) TRI(1); else if (seg <= 2) TRI(2); else if (seg <= 4) TRI(4); else if (seg <= 8) TRI(8); else if (seg <= 16) TRI(16); else TRI(32);
+    if (seg == 1) TRI(1); else if (seg == 2) TRI(2); else if (seg == 4) TRI(4); else if (seg == 8) TRI(8); else if (seg == 16) TRI(16); else TRI(32);
 #undef TRI
     LAUNCHCHK();
     // F T : exponent -, back to z fastest
@@ -1144,20 +1235,6 @@ int32_t nep_wep_sylv_solve(nep_wep_sylv* s, nep_cdouble* dX, nep_stream stream) 
 // coprime factors); NEP_ERR_UNSUPPORTED otherwise (the caller keeps the piecewise route).
 // dMinvH: (M^{-1})^H, mm x mm column-major (nep_gemv_hd applies its conjugate transpose); dG: N x nz, row rz at dG + rz nz.
 }  // extern "C"
-struct SymCfg { int cols = 0, kb = 0, threads = 0; size_t shm = 0; unsigned grid = 0; };
-static bool sylv_sym_cfg(const nep_wep_sylv* s, SymCfg& c) {
-    static const int symcfg = nep_env_int("NEP_WEP_DFT_SYM", 22);
-    c.cols = symcfg / 10; c.kb = symcfg % 10;
-    if (!(symcfg && (s->N1 & 1) && (s->N2 & 1) && s->N1 >= 3 && s->N2 >= 3 && (c.cols == 2 || c.cols == 4) && (c.kb == 2 || c.kb == 3)))
-        return false;
-    const int H1 = (s->N1 - 1) / 2, H2 = (s->N2 - 1) / 2;
-    const int items = std::max(((H1 + c.kb - 1) / c.kb) * s->N2, ((H2 + c.kb - 1) / c.kb) * s->N1);
-    c.threads = (items + 63) / 64 * 64;
-    c.shm = ((size_t)c.cols * s->nz + s->N1 + s->N2) * sizeof(cplx);
-    if (c.threads > 512 || c.shm > 150 * 1024) return false;
-    c.grid = (unsigned)((s->nx + c.cols - 1) / c.cols);
-    return true;
-}
 template <bool FWD, int EXPAND>
 static int32_t sylv_dft_sym_launch(nep_wep_sylv* s, const SymCfg& c, double sgn, const cplx* src, cplx* dst, hipStream_t st, DftExpand ex,
                                    int batch = 1) {
@@ -1182,16 +1259,16 @@ template <int MODE>
 static int32_t sylv_tri_launch(nep_wep_sylv* s, hipStream_t st, cplx* T, const cplx* T2, cplx* S, int N, int L, int batch = 1,
                                int64_t tstride = 0, int64_t sstride = 0) {
     const int nz = s->nz, nx = s->nx;
-    const int seg = (nx + 63) / 64;
+    const int seg = wep_seg(nx);
     const dim3 g2((unsigned)((nz + 3) / 4), (unsigned)batch);
-    const size_t shm = MODE == 1 ? (size_t)4 * nx * sizeof(cplx) : 0;
+    const size_t shm = MODE == 1 ? wep_rowbuf_shm(nx) : 0;
 #define TRIX(S_)                                                                                                              \
     do {                                                                                                                      \
         static thread_local bool attr = false;                                                                                \
         if (MODE == 1 && !attr) { HIPCHK(hipFuncSetAttribute((const void*)k_tridiag_modes<S_, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); attr = true; } \
         hipLaunchKernelGGL((k_tridiag_modes<S_, MODE>), g2, dim3(256), shm, st, nz, nx, (const cplx*)s->d_m, (const cplx*)s->d_dinv, s->b, T, T2, S, N, L, tstride, sstride); \
     } while (0)
-    if (seg <= 1) TRIX(1); else if (seg <= 2) TRIX(2); else if (seg <= 4) TRIX(4); else if (seg <= 8) TRIX(8); else if (seg <= 16) TRIX(16); else TRIX(32);
+    if (seg == 1) TRIX(1); else if (seg == 2) TRIX(2); else if (seg == 4) TRIX(4); else if (seg == 8) TRIX(8); else if (seg == 16) TRIX(16); else TRIX(32);
 #undef TRIX
     LAUNCHCHK();
     return NEP_OK;
@@ -1205,7 +1282,7 @@ int32_t nep_wep_smw_apply(nep_wep_sylv* s, nep_wep_pinv* p, int32_t N, const nep
                           nep_stream stream) {
     ARGCHK(s && p && dKsc && d_sinv && dMinvH && dG && dR && N >= 1 && s->nz % N == 0 && s->nx == s->nz + 4 && p->nz == s->nz);
     SymCfg c;
-    if (!sylv_sym_cfg(s, c) || (size_t)4 * s->nx * sizeof(cplx) > 150 * 1024) return NEP_ERR_UNSUPPORTED;
+    if (!wep_smw_cfg(s->nz, s->nx, s->N1, s->N2, c)) return NEP_ERR_UNSUPPORTED;
     hipStream_t st = as_stream(stream);
     const int nz = s->nz, nx = s->nx, mm = N * (N + 4), L = nz / N;
     const size_t tsz = (size_t)nz * s->ldt;
@@ -1283,7 +1360,7 @@ int32_t nep_wep_smw_matrix_modes(nep_wep_sylv* s, nep_wep_pinv* p, int32_t N, co
                                  const nep_cdouble* d_sinv, const nep_cdouble* dG, nep_cdouble* dM, nep_stream stream) {
     ARGCHK(s && p && dKsc && d_sinv && dG && dM && N >= 1 && s->nz % N == 0 && s->nx == s->nz + 4 && p->nz == s->nz);
     SymCfg c;
-    if (!sylv_sym_cfg(s, c) || (size_t)4 * s->nx * sizeof(cplx) > 150 * 1024) return NEP_ERR_UNSUPPORTED;
+    if (!wep_smw_cfg(s->nz, s->nx, s->N1, s->N2, c)) return NEP_ERR_UNSUPPORTED;
     hipStream_t st = as_stream(stream);
     const int nz = s->nz, mm = N * (N + 4), L = nz / N;
     const int64_t tsz = (int64_t)nz * s->ldt, ssz = (int64_t)nz * (N + 4);
