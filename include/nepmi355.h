@@ -189,6 +189,24 @@ int32_t nep_lr_hankel(nep_spmf* s, int32_t ma, int32_t mb, const nep_cdouble* dW
                       int64_t ldb, const nep_cdouble* dTau, int64_t ldt, nep_cdouble* h_c, nep_cdouble* d_c,
                       nep_stream stream);
 
+/* Expansion step of compute_Mlincomb on a deflated NEP (Effenberger deflation).  With X = V0 (n0 x p), V = [V1; V2]
+ * (k columns of n0 + p rows), s = startder, K = k + s, e_i = i + s:
+ *   Vn[:, j] = [j >= s] a_{j-s} V1[:, j-s] + X sum_{i : e_i >= j} G[i, j] W_{e_i - j} V2[:, i],   j = 0..K-1
+ *   zb       = a_0 X^H V1[:, 0] for s == 0, zeros for s > 0          (always written)
+ * and sum_j M^(j)(lambda) Vn[:, j] (nep_mlincomb with a block of ones) is the top part of the deflated product.
+ * replaces: compute_Mlincomb(::DeflatedGenericNEP, ...) src/nep_deflation.jl:65-107 (Q[i] by repeated solves with the factors of
+ *           lambda I - S, Z[:, j] += factor * Xhat * Vnew, Vnew = V[1:n0, :] * Diagonal(a) + Z, z_bottom = X' * V[1:n0, 1] * a[1]).
+ * The host supplies W_d = (lambda I - S0)^-(d+1) and G[i, j] = (-1)^(e_i - j) a_i e_i! / j!; the kernels use the tables as
+ * given.  hA (k), hG (k x K, column-major), hW (p x p x K: W_d at hW + d p^2, column-major) are host arrays that may be freed
+ * on return (staged like nep_mlincomb's hC).  dV is not modified; dVn (n0 x K, ldo) must not overlap dV; rows beyond n0
+ * (n0 + p for dV) of a column are neither read nor written.  Asynchronous; at most three launches (two for K <= 8), fixed
+ * reduction order, no atomics: two calls give the same bits.
+ * NEP_ERR_UNSUPPORTED (nothing launched) unless 1 <= p <= 32 and k + s <= 64; NEP_ERR_ARG (nothing launched) for n0 < 1, k < 1,
+ * s < 0, ldx < n0, ldo < n0, ldv < n0 + p. */
+int32_t nep_defl_expand(int64_t n0, int32_t p, int32_t k, int32_t s, const nep_cdouble* dX, int64_t ldx,
+                        const nep_cdouble* dV, int64_t ldv, const nep_cdouble* hA, const nep_cdouble* hG,
+                        const nep_cdouble* hW, nep_cdouble* dVn, int64_t ldo, nep_cdouble* dzb, nep_stream stream);
+
 /* K2  residual batch: r_s = sum_i F[i,s] A_i q_s, s=1..k; returns ||r_s||_2 and ||q_s||_2.
  * replaces: k calls of estimate_error -> compute_Mlincomb(nep,lambda_s,q_s)
  *           src/errmeasure.jl:128-130,186-190; call sites src/method_iar.jl:134-135,

@@ -26,6 +26,8 @@ from .jd import jd_betcke, jd_eig_sorter
 from .newton import resinv, quasinewton, augnewton, compute_rf, armijo_rule, ScalarNewtonInnerSolver
 from .twosided import rfi, transpose_relation, twosided_linsolvers
 from .infbilanczos import infbilanczos, left_right_scalar_prod
+from .deflation import (deflate_eigpair, get_deflated_eigpairs, normalize_schur_pair, verify_deflate_mode, DeflatedNEPMM,
+                        DeflatedGenericNEP, DeflatedSPMF)
 from .projection import (Proj_SPMF_NEP, create_proj_NEP, inner_solve, InnerSolver, DefaultInnerSolver, IARInnerSolver,
                          NewtonInnerSolver, IARChebInnerSolver, PolyeigInnerSolver, polyeig)
 from .nleigs import nleigs, NleigsSolutionDetails

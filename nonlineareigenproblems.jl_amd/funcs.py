@@ -200,6 +200,50 @@ class Affine(ScalarFun):
         return self.f.values(self.scale * np.asarray(lams, dtype=np.complex128) + self.shift)
 
 
+class Resolvent(ScalarFun):
+    """g(lam) = f(lam) / (lam - mu): the functions of the rank-one terms of a deflated SPMF (the reference's closure
+    `S -> (S - mu*one(S)) \\ f(S)`, src/nep_deflation.jl:259).  Differentiating (lam - mu) g = f j times gives
+    (lam - mu) g^(j) + j g^(j-1) = f^(j), so with G_j = scale^j g^(j) and F_j = scale^j f^(j)
+
+        G_j = (F_j - j scale G_{j-1}) / (lam - mu),        T_j = G_j / j! = (F_j / j! - scale T_{j-1}) / (lam - mu):
+
+    Leibniz' rule as a two-term recurrence in which neither j!, scale^j nor a power of (lam - mu) appears on its own."""
+
+    def __init__(self, f, mu):
+        self.f, self.mu = f, mu
+
+    def real_on_reals(self):
+        return self.f.real_on_reals() and complex(self.mu).imag == 0
+
+    def derivs(self, lam, k, scale=1.0):
+        F = self.f.derivs(lam, k, scale)
+        w = complex(lam) - self.mu
+        out = np.empty(k, dtype=np.complex128)
+        g = 0j
+        for j in range(k):
+            g = (F[j] - (j * scale) * g) / w
+            out[j] = g
+        return out
+
+    def taylor(self, lam, k, scale=1.0):
+        F = self.f.taylor(lam, k, scale)
+        w = complex(lam) - self.mu
+        out = np.empty(k, dtype=np.complex128)
+        g = 0j
+        for j in range(k):
+            g = (F[j] - scale * g) / w
+            out[j] = g
+        return out
+
+    def matfun(self, S):
+        S = np.asarray(S, dtype=complex)
+        return np.linalg.solve(S - self.mu * np.eye(S.shape[0]), self.f.matfun(S))
+
+    def values(self, lams):
+        lams = np.asarray(lams, dtype=np.complex128)
+        return self.f.values(lams) / (lams - self.mu)
+
+
 class Sum(ScalarFun):
     def __init__(self, *fs):
         self.fs = fs

@@ -221,6 +221,29 @@ def pep0(n=200):
 GALLERY["pep0"] = pep0
 
 
+def gen_rng_spmat(rng, n, m, p):
+    """src/gallery_extra/basic_random_examples.jl:107-128: round(p m n) draws of (row, column, value), a later draw of the
+    same position replacing the earlier one"""
+    entries = {}
+    for _ in range(int(round(p * m * n))):
+        r = rng.gen_rng_int() % n
+        c = rng.gen_rng_int() % m
+        entries[(r, c)] = 1 - 2 * rng.gen_rng_float()
+    rc = np.array(list(entries.keys()), dtype=np.int64).reshape(-1, 2)
+    return sp.csc_matrix((np.array(list(entries.values()), dtype=float), (rc[:, 0], rc[:, 1])), shape=(n, m))
+
+
+def dep0_sparse(n=100, p=0.25):
+    """src/gallery_extra/basic_random_examples.jl:13-20: DEP with sparse random matrices (random diagonal + gen_rng_spmat)"""
+    rng = MSWS_RNG()
+    A0 = sp.diags(gen_rng_mat(rng, n, 1)[:, 0]) + gen_rng_spmat(rng, n, n, p)
+    A1 = sp.diags(gen_rng_mat(rng, n, 1)[:, 0]) + gen_rng_spmat(rng, n, n, p)
+    return DEP([sp.csc_matrix(A0), sp.csc_matrix(A1)], [0.0, 1.0])
+
+
+GALLERY["dep0_sparse"] = dep0_sparse
+
+
 def particle_nep(interval):
     """The "particle in a canyon" problem of test/nleigs/particle_test_utils.jl:37-165 (after W. Vandenberghe): a 2-D
     Schroedinger operator H - lam I on a 201 x 81 grid plus, per branch point (eigenvalue of the lead Hamiltonian), a

@@ -549,11 +549,13 @@ class AbstractSPMF(NEP):
                 Fs.append(np.diag(np.array([f(s) for s in np.diag(S)], dtype=np.complex128)))
             else:
                 Fs.append(np.asarray(f.matfun(S), dtype=np.complex128))
-        B = np.hstack(Fs)                                    # p x (p*mt)
         mt = len(fv)
-        XT = gemm_ts(Vd, B, rowmajor=True)                   # (n, p*mt) row-major
         ZT = torch.empty((self.n, p), dtype=CDT, device="cuda")
-        check(lib.nep_spmm_terms(self.dev.h, p, c_vp(XT.data_ptr()), p * mt, c_vp(ZT.data_ptr()), p, stream_ptr()))
+        for c0 in range(0, p, 256):                          # nep_spmm_terms takes at most 256 columns: wider S in column panels
+            pc = min(256, p - c0)
+            B = np.hstack([F[:, c0:c0 + pc] for F in Fs])    # p x (pc*mt)
+            XT = gemm_ts(Vd, B, rowmajor=True)               # (n, pc*mt) row-major
+            check(lib.nep_spmm_terms(self.dev.h, pc, c_vp(XT.data_ptr()), pc * mt, c_vp(ZT.data_ptr() + 16 * c0), p, stream_ptr()))
         if host:
             return self._promote(ZT.cpu().numpy(), S_in, V)
         return ZT.t().contiguous()
