@@ -207,6 +207,23 @@ int32_t nep_defl_expand(int64_t n0, int32_t p, int32_t k, int32_t s, const nep_c
                         const nep_cdouble* dV, int64_t ldv, const nep_cdouble* hA, const nep_cdouble* hG,
                         const nep_cdouble* hW, nep_cdouble* dVn, int64_t ldo, nep_cdouble* dzb, nep_stream stream);
 
+/* Border step of a linear solve with the deflated matrix [M(lambda) U; X^H 0], U = M(lambda) X (lambda I - S0)^-1, X^H X = I.
+ * Because M^-1 U = X (lambda I - S0)^-1 exactly, the Schur complement -X^H M^-1 U is -(lambda I - S0)^-1 and the solution of
+ * [M U; X^H 0] [v1; v2] = [b1; b2] is
+ *   y = M(lambda)^-1 b1 (ONE solve with the original matrix, the caller's),  c = b2 - X^H y,  v1 = y + X c,  v2 = -(lambda I - S0) c
+ * (check: M v1 + U v2 = b1 + M X c - M X c = b1, X^H v1 = X^H y + c = b2).  This call computes, from y,
+ *   c = b2 - X^H y,   out[0:n0] = scale (y + X c),   out[n0:n0+p] = scale (T c).
+ * replaces: lin_solve(::DeflatedNEPLinSolver) src/LinSolvers.jl:221-252 (p + 1 solves with the original solver, Z = M^-1 U,
+ *           S = -X' Z, v2 = S \ (b2 - X' b1tilde), v1 = b1tilde - Z v2).
+ * dX: n0 x p column-major (ldx), dY: n0 entries, db2: p device entries or NULL (zeros), hT: p x p column-major HOST table (the
+ * caller passes -(lambda I - S0); may be freed on return, staged like nep_defl_expand's tables; the kernels use it as given).
+ * dOut: n0 + p entries; dY may be dOut itself (in place); db2 must not overlap dOut.  Asynchronous; three launches, fixed
+ * reduction order, no atomics: two calls give the same bits.
+ * NEP_ERR_UNSUPPORTED (nothing launched) unless 1 <= p <= 32; NEP_ERR_ARG (nothing launched) for n0 < 1, ldx < n0, a NULL
+ * dX / dY / hT / dOut, or db2 overlapping dOut. */
+int32_t nep_defl_border(int64_t n0, int32_t p, const nep_cdouble* dX, int64_t ldx, const nep_cdouble* dY,
+                        const nep_cdouble* db2, const nep_cdouble* hT, double scale, nep_cdouble* dOut, nep_stream stream);
+
 /* K2  residual batch: r_s = sum_i F[i,s] A_i q_s, s=1..k; returns ||r_s||_2 and ||q_s||_2.
  * replaces: k calls of estimate_error -> compute_Mlincomb(nep,lambda_s,q_s)
  *           src/errmeasure.jl:128-130,186-190; call sites src/method_iar.jl:134-135,

@@ -13,7 +13,8 @@ from .nep import (NEP, AbstractSPMF, SPMF_NEP, DEP, PEP, SumNEP, DerSPMF, shift_
                   to_dev, to_host)
 from .linsolvers import (LinSolver, FactorizeLinSolver, BackslashLinSolver, FactorizeLinSolverCreator,
                          BackslashLinSolverCreator, DefaultLinSolverCreator, create_linsolver, lin_solve,
-                         LinSolverCache, DeviceLU, HostLUPool, GMRESLinSolver, GMRESLinSolverCreator, seed_plan_from_rank0)
+                         LinSolverCache, DeviceLU, HostLUPool, GMRESLinSolver, GMRESLinSolverCreator, seed_plan_from_rank0,
+                         DeflatedNEPLinSolver, DeflatedNEPLinSolverCreator)
 from .errmeasure import (Errmeasure, ResidualErrmeasure, StandardSPMFErrmeasure, DefaultErrmeasure,
                          estimate_error, estimate_errors)
 from .dense import gemm_ts, orthogonalize_and_normalize, DGKS, CGS, MGS
@@ -22,7 +23,7 @@ from .tiar import tiar
 from .iar_chebyshev import iar_chebyshev
 from .ilan import ilan
 from .nlar import nlar, residual_eigval_sorter, default_eigval_sorter
-from .jd import jd_betcke, jd_eig_sorter
+from .jd import jd_betcke, jd_effenberger, jd_eig_sorter
 from .newton import resinv, quasinewton, augnewton, compute_rf, armijo_rule, ScalarNewtonInnerSolver
 from .twosided import rfi, transpose_relation, twosided_linsolvers
 from .infbilanczos import infbilanczos, left_right_scalar_prod

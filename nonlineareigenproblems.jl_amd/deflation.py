@@ -22,7 +22,8 @@ in three representations (the reference's `mode`):
 
 The linear systems of the Newton-type drivers are solved with the bordered matrix assembled and factorised as a whole
 (compute_Mder + DeviceLU, like any NEP): at a deflated eigenvalue M(sigma) is singular while Mt(sigma) is not, so block
-elimination on the factors of M(sigma) is not an option.
+elimination on the factors of M(sigma) is not an option.  jd_effenberger, whose shifts head for a NEW eigenvalue,
+opts into block elimination with one solve of M(sigma): linsolvers.DeflatedNEPLinSolver.
 """
 import math
 import warnings

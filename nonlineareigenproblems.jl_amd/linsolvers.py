@@ -1161,3 +1161,97 @@ class GMRESLinSolverCreator(LinSolverCreator):
 
     def __init__(self, **kwargs):
         self.kwargs = kwargs
+
+
+class DeflatedNEPLinSolver(LinSolver):
+    """src/LinSolvers.jl:194-252: solves with the bordered matrix Mt(lam) = [M U; X^H 0] of a deflated NEP, recycling the linear
+    solver of the ORIGINAL NEP.  The reference forms the Schur complement S = -X^H M^-1 U with p + 1 solves; with X^H X = I
+    (normalize_schur_pair) and U = M X (lam I - S0)^-1, M^-1 U = X (lam I - S0)^-1 exactly, so S = -(lam I - S0)^-1 and
+
+        y = M^-1 b1,   c = b2 - X^H y,   v1 = y + X c,   v2 = -(lam I - S0) c
+
+    is ONE solve with the original solver plus one pass over X (nep_defl_border, csrc/deflate_border.hip).  Works for the three
+    deflation modes alike (only orgnep, S0 and V0 are used).  Like the reference's, the solve is as accurate as M(lam) is
+    conditioned: the solver is for shifts away from the deflated eigenvalues (jd_effenberger's iterates); at a deflated
+    eigenvalue use the deflated NEP's own solver, which factorises the bordered matrix as a whole."""
+
+    def __init__(self, deflated_nep, lam, orglinsolver):
+        self.deflated_nep = deflated_nep
+        self.lam = complex(lam)
+        self.orglinsolver = orglinsolver
+        self._Xd = None
+
+    @property
+    def Xd(self):
+        if self._Xd is None:
+            d = self.deflated_nep
+            self._Xd = d.Xd if hasattr(d, "Xd") else to_dev(d.V0)       # (p, n0): column-major n0 x p
+        return self._Xd
+
+    def _table(self):
+        d = self.deflated_nep
+        return _lib.as_c128(d.S0 - self.lam * np.eye(d.p), "F")         # -(lam I - S0)
+
+    def _border_fused(self, x, b2, T, scale):
+        """x (n0 + p entries, the first n0 holding y) -> scale [v1; v2] in place by nep_defl_border; False for p > 32"""
+        d = self.deflated_nep
+        rc = lib.nep_defl_border(d.n0, d.p, c_vp(self.Xd.data_ptr()), d.n0, c_vp(x.data_ptr()),
+                                 c_vp(b2.data_ptr()) if b2 is not None else None, hptr(T), float(scale), c_vp(x.data_ptr()),
+                                 stream_ptr())
+        if rc == _lib.NEP_ERR_UNSUPPORTED:
+            return False
+        check(rc)
+        return True
+
+    def _border_composed(self, x, b2, T, scale):
+        """the same result from existing device primitives, for p > 32: c = b2 - X^H y by nep_gemv_hd and nep_axpy, T c and
+        X c by the GEMM with a device B, nep_axpy and nep_scal.  Nothing is copied to the host."""
+        from . import dense
+        d = self.deflated_nep
+        n0, p = d.n0, d.p
+        c = torch.empty(p, dtype=CDT, device="cuda")
+        check(lib.nep_gemv_hd(c_vp(self.Xd.data_ptr()), n0, n0, p, c_vp(x.data_ptr()), None, c_vp(c.data_ptr()), stream_ptr()))
+        dense.scal(c, -1.0, p)
+        if b2 is not None:
+            dense.axpy(1.0, b2, c, p)
+        Xc = dense.gemm_ts_dev(self.Xd, c, 1, p, k=p, rows=n0, ldz=n0)             # (1, n0)
+        dense.axpy(1.0, Xc, x, n0)
+        Td = to_dev(T)                                                               # (p, p): column-major T
+        dense.gemm_ts_dev(Td, c, 1, p, out=x[n0:].reshape(1, p), k=p, rows=p, ldz=p)
+        if scale != 1.0:
+            dense.scal(x, scale, n0 + p)
+
+    def solve_dev(self, b, out=None, scale=1.0):
+        """device solve; b: (n0 + p,) or (nrhs, n0 + p) tensor; out may alias b"""
+        d = self.deflated_nep
+        n0, p, n = d.n0, d.p, d.n
+        if b.dim() == 2 and b.shape[0] > 1:
+            X = torch.empty_like(b) if out is None else out
+            for j in range(b.shape[0]):
+                self.solve_dev(b[j], out=X[j], scale=scale)
+            return X
+        if b.numel() != n or not b.is_contiguous():
+            raise ValueError("b must have %d entries" % n)
+        X = torch.empty_like(b) if out is None else out
+        bv, x = b.reshape(n), X.reshape(n)
+        b2 = bv[n0:]
+        if b2.data_ptr() + 16 * p > x.data_ptr() and x.data_ptr() + 16 * n > b2.data_ptr():
+            b2 = b2.clone()                                   # out is b (or overlaps its tail): the p tail entries are kept first
+        self.orglinsolver.solve_dev(bv[:n0], out=x[:n0])
+        T = self._table()
+        if not self._border_fused(x, b2, T, scale):
+            self._border_composed(x, b2, T, scale)
+        return X.reshape(b.shape)
+
+
+class DeflatedNEPLinSolverCreator(LinSolverCreator):
+    """src/LinSolverCreators.jl:149-181: creates the solver of the original NEP with `orglinsolvercreator` and wraps it"""
+
+    def __init__(self, orglinsolvercreator=None):
+        self.orglinsolvercreator = DefaultLinSolverCreator() if orglinsolvercreator is None else orglinsolvercreator
+
+    def create_linsolver(self, nep, lam):
+        from .deflation import DeflatedGenericNEP, DeflatedNEPMM, DeflatedSPMF
+        if not isinstance(nep, (DeflatedGenericNEP, DeflatedNEPMM, DeflatedSPMF)):
+            raise TypeError("DeflatedNEPLinSolverCreator needs a deflated NEP (deflate_eigpair), got %s" % type(nep).__name__)
+        return DeflatedNEPLinSolver(nep, lam, create_linsolver(self.orglinsolvercreator, nep.orgnep, lam))
