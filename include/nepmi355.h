@@ -224,6 +224,23 @@ int32_t nep_defl_expand(int64_t n0, int32_t p, int32_t k, int32_t s, const nep_c
 int32_t nep_defl_border(int64_t n0, int32_t p, const nep_cdouble* dX, int64_t ldx, const nep_cdouble* dY,
                         const nep_cdouble* db2, const nep_cdouble* hT, double scale, nep_cdouble* dOut, nep_stream stream);
 
+/* The small products of a compact rational Krylov (CORK) step:
+ *   Out[rho, gam] = alpha u[rho] g[gam] + sum_{q < k} U[rho, q] G[q, gam],   rho < r, gam < c.
+ * replaces: src/method_AAAeigs.jl:283-287,332-339 (u_c = U[1:r,1:k,j] * (compactB * [I; Y[2:end,:]]) after the k x k solve for Y,
+ *           and W = [u1_hat  U[1:rnew,:,j] * compactB[:,l+1:end]], Uhat = W / MlNfact).  With the tables of a shift formed once
+ *           on the host (C_sigma = B[:, :l] + B[:, l:] Y[1:, :];  g_sigma = (Mext^-1)[0, :], G_sigma = B[:, l:] (Mext^-1)[1:, :])
+ *           u_c is the call with dG = C_sigma and du = NULL, Uhat the call with dG = G_sigma, dg = g_sigma and du = the row
+ *           [Q^H v; ||v_perp||] that nep_orth_dev leaves on the device; alpha carries the scaling of :296-300.
+ * dU: r x k column-major (ldu), dG: k x c column-major (ldg), du: r device entries or NULL (no rank-1 term), dg: c device
+ * entries (read only with du), alpha by value, dOut: r x c column-major (ldo); dOut must not overlap dU, dG, du or dg.  Rows
+ * >= r of a column and the padding behind a column are neither read nor written.  Asynchronous; ONE launch, no atomics, fixed
+ * summation order (q ascending, then the rank-1 term): two calls give the same bits.
+ * NEP_ERR_UNSUPPORTED (nothing launched) unless 1 <= k <= 256 and 1 <= c <= 256; NEP_ERR_ARG (nothing launched) for r < 1,
+ * ldu < r, ldg < k, ldo < r, a NULL dU / dG / dOut, du without dg, or dOut overlapping an input. */
+int32_t nep_cork_expand(int32_t r, int32_t k, int32_t c, const nep_cdouble* dU, int64_t ldu, const nep_cdouble* dG, int64_t ldg,
+                        const nep_cdouble* du, const nep_cdouble* dg, nep_cdouble alpha, nep_cdouble* dOut, int64_t ldo,
+                        nep_stream stream);
+
 /* K2  residual batch: r_s = sum_i F[i,s] A_i q_s, s=1..k; returns ||r_s||_2 and ||q_s||_2.
  * replaces: k calls of estimate_error -> compute_Mlincomb(nep,lambda_s,q_s)
  *           src/errmeasure.jl:128-130,186-190; call sites src/method_iar.jl:134-135,

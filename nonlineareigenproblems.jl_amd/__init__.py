@@ -32,6 +32,7 @@ from .deflation import (deflate_eigpair, get_deflated_eigpairs, normalize_schur_
 from .projection import (Proj_SPMF_NEP, create_proj_NEP, inner_solve, InnerSolver, DefaultInnerSolver, IARInnerSolver,
                          NewtonInnerSolver, IARChebInnerSolver, PolyeigInnerSolver, polyeig)
 from .nleigs import nleigs, NleigsSolutionDetails
+from .aaaeigs import AAAeigs, svAAA, AAASolutionDetails
 from . import rk_helper
 from .contour import (contour_beyn, contour_block_SS, integrate_interval, MatrixIntegrator, MatrixTrapezoidal,
                       MatrixTrapezoidalSharded, probe_block)
