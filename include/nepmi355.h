@@ -241,6 +241,25 @@ int32_t nep_cork_expand(int32_t r, int32_t k, int32_t c, const nep_cdouble* dU, 
                         const nep_cdouble* du, const nep_cdouble* dg, nep_cdouble alpha, nep_cdouble* dOut, int64_t ldo,
                         nep_stream stream);
 
+/* One pass over the approximate inverse Jacobian T of Broyden's method (n x n, column-major, ldt, device):
+ *   T[i, j] += u0[i] a0[j]                     when du0 / da0 are given: the only write to T
+ *   y[i]     = sum_j T_new[i, j] x[j]          when dx / dy are given
+ *   g[j]     = sum_i conj(w[i]) T_new[i, j]    when dw / dg are given: the ROW w^H T_new, unconjugated
+ * replaces: src/method_broyden.jl:69,101,107,117 (Trk = T*rk, Tztilde = T*ztilde, dv'*T and T = T + Tztilde*aH: four passes over
+ *           T per inner iteration).  a0 holds the row aH as it stands (no conjugation here); with the update of iteration j kept
+ *           pending, the sweep of iteration j + 1 applies it and returns T*ztilde and dv'*T of the updated matrix.
+ * du0, da0, dx, dw: n device entries each; dy, dg: n device entries, written; dWork: nep_broyden_sweep_worksize(n) complex
+ * device entries of scratch (per-tile partial sums).  dy and dg must not overlap each other, an input, dT or dWork; dWork must
+ * not overlap dT.  Every entry of T is read once, written once with an update and never without; rows >= n of a column and the
+ * padding behind it are neither read nor written.  Asynchronous; at most two launches, no atomics, fixed summation order: two
+ * calls on equal inputs give the same bits.
+ * NEP_ERR_ARG (nothing launched) for n < 1, ldt < n, a NULL dT / dWork, one half of a pair without the other, no work
+ * requested, or an overlap named above. */
+int64_t nep_broyden_sweep_worksize(int64_t n);
+int32_t nep_broyden_sweep(int64_t n, nep_cdouble* dT, int64_t ldt, const nep_cdouble* du0, const nep_cdouble* da0,
+                          const nep_cdouble* dx, nep_cdouble* dy, const nep_cdouble* dw, nep_cdouble* dg, nep_cdouble* dWork,
+                          nep_stream stream);
+
 /* K2  residual batch: r_s = sum_i F[i,s] A_i q_s, s=1..k; returns ||r_s||_2 and ||q_s||_2.
  * replaces: k calls of estimate_error -> compute_Mlincomb(nep,lambda_s,q_s)
  *           src/errmeasure.jl:128-130,186-190; call sites src/method_iar.jl:134-135,

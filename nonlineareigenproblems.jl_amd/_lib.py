@@ -104,6 +104,8 @@ SIGNATURES = {
     "nep_defl_expand": [c_i64, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp],
     "nep_defl_border": [c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp],
     "nep_cork_expand": [c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, cdouble, c_vp, c_i64, c_vp],
+    "nep_broyden_sweep_worksize": [c_i64],
+    "nep_broyden_sweep": [c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "nep_resid_batch": [c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
     "nep_resid_batch_dev": [c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp],
     "nep_resid_block": [c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
@@ -204,7 +206,7 @@ SIGNATURES = {
 for _name, _args in SIGNATURES.items():
     _f = getattr(lib, _name)  # AttributeError here = header/library mismatch
     _f.argtypes = _args
-    _f.restype = C.c_char_p if _name in ("nep_last_error", "nep_src_digest") else c_i32
+    _f.restype = C.c_char_p if _name in ("nep_last_error", "nep_src_digest") else c_i64 if _name == "nep_broyden_sweep_worksize" else c_i32
 
 
 def check(status):

@@ -2,6 +2,7 @@
 for the problems on the hot path.
 
   "dep0"              src/gallery_extra/basic_random_examples.jl:2-9 (MSWS RNG :73-105)
+  "dep1"              src/gallery_extra/gallery_examples.jl:2-10
   "qdep0"             src/gallery_extra/gallery_examples.jl:75-88 (matrices: data/qdep0.npz)
   "nlevp_native_gun"  src/gallery_extra/NLEVP_native.jl:4-18.  gun_K/gun_M are missing from the
                       reference checkout (.MISSING_LARGE_BLOBS); they are read from $NEPMI_GUN_DIR in
@@ -174,6 +175,14 @@ def dep0(n=5):
     return DEP([A0, A1], [0.0, 1.0])
 
 
+def dep1():
+    """src/gallery_extra/gallery_examples.jl:2-10: a 3 x 3 delay eigenvalue problem with one eigenvalue equal to one"""
+    A0 = np.array([[1.0, 2.0, 3.0], [4.0, 5.0, 6.0], [1.0, -1.0, 3.0]])
+    A1 = (-A0 + np.array([[1.0, 0.0, 3.0], [0.0, 0.0, -1.0], [0.0, 0.0, 10.0]])) * np.exp(1.0)
+    Q = np.array([[1.0, 0.0, 3.0], [1.0, 1.0, -4.0], [2.0, 3.0, 1.0]])
+    return DEP([np.linalg.solve(Q, A0 @ Q), np.linalg.solve(Q, A1 @ Q)], [0.0, 1.0])
+
+
 def qdep0():
     p = os.path.join(_DATA, "qdep0.npz")
     A0 = _load_csc(p, "A0"); A1 = _load_csc(p, "A1")
@@ -189,6 +198,7 @@ def _wep(**kw):
 GALLERY = {
     "WEP": _wep,
     "dep0": dep0,
+    "dep1": dep1,
     "qdep0": qdep0,
     "nlevp_native_gun": nlevp_native_gun,
     "gun_spmf": gun_spmf,
