@@ -314,14 +314,17 @@ int32_t nep_spmm_terms(nep_spmf* s, int32_t p, const nep_cdouble* dXT, int64_t l
  * h = V^H w; w -= V h; [DGKS: while ||w|| < ||corr||/sqrt(2): corr=V^H w; w-=V corr; h+=corr];
  * beta=||w||; w/=beta.   dV: rows x k (ldv).  h_active_rows (nullable, k entries): number of
  * leading rows of column j that can be non-zero (iar's block-triangular basis); rows beyond are
- * skipped.  method: 0 = DGKS, 1 = classical GS (one pass), 2 = modified GS.  Synchronous. */
+ * skipped.  Contract: column j of dV must HOLD zeros in the rows active[j] .. rows - 1 -- the projection masks them per row, the
+ * update skips whole tiles only and reads them inside a partly active tile.  Entries above rows count as rows.
+ * method: 0 = DGKS, 1 = classical GS (one pass), 2 = modified GS.  Synchronous.  A vector inside span(V) (||w|| == 0 after the
+ * update) returns NEP_ERR_BREAKDOWN with h, *h_beta = 0 and *h_npasses set and w left at zero. */
 int32_t nep_orth(const nep_cdouble* dV, int64_t ldv, int64_t rows, int32_t k,
                  const int64_t* h_active_rows, nep_cdouble* dw, nep_cdouble* h_h, double* h_beta,
                  int32_t method, int32_t* h_npasses, nep_stream stream);
 /* asynchronous DGKS (method 0) / CGS (method 1): no host synchronisation.  The re-orthogonalisation passes are
  * always enqueued and gate themselves on the device with the same criterion (at most 2 passes, NEP_ORTH_DEV_PASSES); w is normalised on the
- * device.  d_active_rows: DEVICE array (or NULL).  d_out (k+2 complex, device): h[0..k), (beta, 0),
- * (passes, 2*breakdown + another_pass_wanted). */
+ * device.  d_active_rows: DEVICE array (or NULL), same contract as nep_orth: dV holds zeros at and below active[j].  d_out (k+2
+ * complex, device): h[0..k), (beta, 0), (passes, 2*breakdown + another_pass_wanted).  method 2: NEP_ERR_ARG. */
 int32_t nep_orth_dev(const nep_cdouble* dV, int64_t ldv, int64_t rows, int32_t k, const int64_t* d_active_rows,
                      nep_cdouble* dw, nep_cdouble* d_out, int32_t method, nep_stream stream);
 /* h = V^H w for a rows x k block (w untouched, k host results, synchronous): the products W^H (A_i v) behind
@@ -330,7 +333,8 @@ int32_t nep_gemv_h(const nep_cdouble* dV, int64_t ldv, int64_t rows, int32_t k, 
                    nep_cdouble* h_h, nep_stream stream);
 /* K9  C = W^H Y (k x p, host, column-major) for two ROW-major device blocks WT (rows x k), YT (rows x p), k, p <= 256:
  * all of B_i = W^H (A_i V) at once (YT from nep_resid_block with F = e_i 1^T), FP64 MFMA with the row index as contraction
- * index, per-workgroup partial tiles summed in a fixed order.  Synchronous. */
+ * index, per-workgroup partial tiles summed in a fixed order.  Synchronous.  ldw >= k, ldy >= p: the padding behind the k (p)
+ * entries of a row is never read; dWT and dYT may be the same block (Gram matrix). */
 int32_t nep_gemm_h_rm(const nep_cdouble* dWT, int64_t ldw, const nep_cdouble* dYT, int64_t ldy, int64_t rows,
                       int32_t k, int32_t p, nep_cdouble* h_C, nep_stream stream);
 
