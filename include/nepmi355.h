@@ -307,6 +307,24 @@ int32_t nep_resid_block(nep_spmf* s, int32_t k, const nep_cdouble* hF, const nep
 int32_t nep_spmm_terms(nep_spmf* s, int32_t p, const nep_cdouble* dXT, int64_t ldx,
                        nep_cdouble* dZT, int64_t ldz, nep_stream stream);
 
+/* K12  SPMF block product with per-term tables:
+ *   Z[:, 0:q] = beta Z[:, 0:q] + alpha sum_{t < mt} A_t (Y G_t),     Y: n x r,  G_t: r x q,  Z: n x q  (column-major)
+ * replaces: compute_MM(::SPMF_NEP,S,V) src/NEPTypes.jl:276-319 for G_t = f_t(S), and the term loops of the block Newton
+ *           method, src/method_blocknewton.jl:173-179 (T12 = T12 + Av[j]*X*DF1) and :201-206 (RT[:,i+1:p] += -Av[j]*(Za+Zb)),
+ *           where G_t is a block of f_t on an expanded matrix -- composed from nep_gemm_ts (row-major n x (mt q) block),
+ *           nep_spmm_terms and a transpose back otherwise: three launches and 16 n mt q bytes written and read again.
+ * dY (ldy >= n) is not modified.  hG: host array, G_t column-major at hG + t r q; it may be freed on return (staged through
+ * the handle's pinned ring into a device slot of the handle that is not handed out again before the kernel that reads it has
+ * finished: calls with different tables may follow each other at once, on any stream).  dZ (ldz >= n) must not overlap dY;
+ * beta == 0: Z is not read (a NaN-filled Z comes back finite), otherwise every entry of Z is read at its own position only.
+ * Rows >= n of a column and the padding behind it are neither read nor written.  Both value widths of the stacked CSR.
+ * Asynchronous; ONE launch, the tables in LDS, no intermediate of size n x (mt q), no atomics, fixed summation order: two
+ * calls on equal inputs give the same bits.
+ * NEP_ERR_UNSUPPORTED (nothing launched) unless 1 <= r <= 32, 1 <= q <= 32 and mt r q <= 3072 (48 KiB of LDS, the budget of
+ * nep_resid_batch_dev); NEP_ERR_ARG (nothing launched) for ldy < n, ldz < n, a NULL s, dY, hG or dZ, or dZ overlapping dY. */
+int32_t nep_spmf_blockprod(nep_spmf* s, int32_t r, int32_t q, const nep_cdouble* dY, int64_t ldy, const nep_cdouble* hG,
+                           nep_cdouble alpha, nep_cdouble beta, nep_cdouble* dZ, int64_t ldz, nep_stream stream);
+
 /* ---- K6 Gram-Schmidt -------------------------------------------------------------------
  * replaces: IterativeSolvers.orthogonalize_and_normalize!(V,w,h,method) (third-party,
  *           IterativeSolvers 0.9.2) at src/method_iar.jl:107, src/method_tiar.jl:128,

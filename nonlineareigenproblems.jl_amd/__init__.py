@@ -34,6 +34,7 @@ from .projection import (Proj_SPMF_NEP, create_proj_NEP, inner_solve, InnerSolve
 from .nleigs import nleigs, NleigsSolutionDetails
 from .aaaeigs import AAAeigs, svAAA, AAASolutionDetails
 from .broyden import broyden, broyden_T
+from .blocknewton import blocknewton
 from . import rk_helper
 from .contour import (contour_beyn, contour_block_SS, integrate_interval, MatrixIntegrator, MatrixTrapezoidal,
                       MatrixTrapezoidalSharded, probe_block)

@@ -226,8 +226,25 @@ struct NepScratch {
     ~NepScratch() { release(); }
 };
 
+// Device slots for small per-call tables that a kernel reads from device memory (blockprod.hip): NSLOT slots of one block, handed
+// out in turn; guard() records an event behind the kernel that reads a slot and acquire() waits for it before the slot is
+// handed out again, so a caller may issue calls with different tables back to back, on any streams.
+struct NepTableSlots {
+    static const int NSLOT = 8;
+    NepScratch dev;
+    hipEvent_t ev[NSLOT] = {nullptr};
+    bool used[NSLOT] = {false};
+    int next = 0;
+    int acquire(size_t slot_bytes, void** dslot, int* which);
+    int guard(int which, hipStream_t st);
+    void release();
+    NepTableSlots() = default;
+    NepTableSlots(const NepTableSlots&) = delete;
+    NepTableSlots& operator=(const NepTableSlots&) = delete;
+};
+
 // spmv.hip: the stacked CSR of an SPMF handle (entries sorted by (col, term) per row) and a scratch block of its own, for
-// kernels in other files (lrprod.hip)
+// kernels in other files (lrprod.hip); the handle's pinned ring and table slots (blockprod.hip)
 struct NepSpmfView {
     int64_t n;
     int32_t mt, valbytes;
@@ -235,5 +252,7 @@ struct NepSpmfView {
     const uint32_t* idx;
     const void* vals;
     NepScratch* scratch;
+    PinnedRing* ring;
+    NepTableSlots* tables;
 };
 extern "C" int nep_spmf_csr_view(nep_spmf* s, NepSpmfView* v);

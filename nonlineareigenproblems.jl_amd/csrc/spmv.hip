@@ -34,6 +34,7 @@ struct nep_spmf {
     NepScratch lrpart;        // nep_lr_hankel's per-workgroup partials (lrprod.hip)
     PinnedRing ring;          // pinned staging of host coefficient blocks
     PinnedRing cwring;        // ... of nep_cw_backward_error (may be called from another host thread than the residual batches)
+    NepTableSlots bptables;   // device slots of nep_spmf_blockprod's G_t tables (blockprod.hip)
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1053,6 +1054,7 @@ int32_t nep_spmf_destroy(nep_spmf* s) {
     s->part.release();
     s->cwpart.release();
     s->lrpart.release();
+    s->bptables.release();
     s->ring.release();
     s->cwring.release();
     delete s;
@@ -1064,6 +1066,8 @@ int nep_spmf_csr_view(nep_spmf* s, NepSpmfView* v) {
     v->n = s->n; v->mt = s->mt; v->valbytes = s->valbytes;
     v->rowptr = s->d_rowptr; v->idx = s->d_idx; v->vals = s->d_vals;
     v->scratch = &s->lrpart;
+    v->ring = &s->ring;
+    v->tables = &s->bptables;
     return NEP_OK;
 }
 
