@@ -13,10 +13,9 @@ the SPMF version (which carries shift and scale) instead of the reference's expl
 import numpy as np
 import torch
 
-from . import dense
+from . import dense, _hosteig
+from ._ritzchecks import RitzChecks
 from .errmeasure import DefaultErrmeasure, estimate_errors
-from .exceptions import NoConvergenceException
-from .iar import _hosteig
 from .linsolvers import DefaultLinSolverCreator, create_linsolver
 from .nep import CDT, DEP, PEP, to_dev, to_host
 
@@ -109,10 +108,9 @@ def iar_chebyshev(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, t
     V[0, :n] = to_dev(v0 / np.linalg.norm(v0))[0]
     z = torch.empty(n, dtype=CDT, device="cuda")
     active = (np.arange(1, m + 2) * n).astype(np.int64)
-    err = np.ones((m, m))
-    lam = np.zeros(0, dtype=np.complex128); QT = None; idx = np.zeros(0, dtype=int)
-    k = 1; conv_eig = 0
-    while k <= m and conv_eig < neigs:
+    checks = RitzChecks(m, tol, neigs, errhist, np.ones((m, m)))
+    k = 1
+    while k <= m and checks.conv_eig < neigs:
         X = V[k - 1][:n * k].view(k, n)                                   # n x k block, column-major, ld n
         vv = V[k]
         dense.gemm_ts(X, L[:k, :k], k=k, rows=n, ldz=n, out=vv[n:(k + 1) * n].view(k, n))       # blocks 1..k = X L
@@ -129,27 +127,8 @@ def iar_chebyshev(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, t
             Dv, Z = _hosteig.eig(H[:k, :k].copy())
             QT = dense.gemm_ts(V, Z, rowmajor=True, k=k, rows=n, ldz=ldv)
             lam = sigma + gamma / Dv
-            e = estimate_errors(errmeasure, lam, QT)
-            conv_eig = int(np.sum(e < tol))
-            idx = np.argsort(e, kind="stable")
-            err[k - 1, :k] = e[idx]
-            if errhist is not None:
-                errhist.append(err[k - 1, :k].copy())
-            if k == m or conv_eig >= neigs:
-                nrof = int(min(len(lam), neigs))
-                lam = lam[idx[:nrof]]
-                idx = idx[:nrof]
+            checks.record(k, lam, QT, estimate_errors(errmeasure, lam, QT))
         k += 1
     k -= 1
-    if conv_eig < neigs and neigs != np.inf:
-        Q = to_host(dense.rowmajor_to_cols(QT, idx[:len(lam)])) if QT is not None else None
-        msg = "Number of iterations exceeded. maxit=%d." % maxit
-        if conv_eig < 3:
-            msg += " Check that σ is not an eigenvalue."
-        raise NoConvergenceException(lam, Q, err[k - 1, :len(lam)], msg)
-    nc = min(len(lam), conv_eig)
-    lam = lam[:nc]
-    Qd = dense.rowmajor_to_cols(QT, idx[:nc])
-    if return_device:
-        return lam, Qd, V[:k]
-    return lam, to_host(Qd), V[:k]
+    lam, Q = checks.finish(k, maxit, " Check that σ is not an eigenvalue.", None if return_device else to_host)
+    return lam, Q, V[:k]

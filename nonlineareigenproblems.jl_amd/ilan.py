@@ -16,11 +16,10 @@ same iterates); the SPMF version is used for every SPMF-type NEP here.
 import numpy as np
 import torch
 
-from . import dense, _lib
+from . import dense, _lib, _hosteig
 from ._lib import lib, check, hptr, c_vp
 from .errmeasure import DefaultErrmeasure, estimate_errors
 from .exceptions import NoConvergenceException
-from .iar import _hosteig
 from .linsolvers import DefaultLinSolverCreator, create_linsolver
 from .nep import CDT, to_dev, to_host, stream_ptr
 

@@ -28,6 +28,7 @@ import torch
 from . import dense, rk_helper as rk
 from ._lib import lib, check, hptr, c_vp
 from .errmeasure import ResidualErrmeasure, estimate_errors
+from .iar import _OrthPassMiss
 from .linsolvers import DefaultLinSolverCreator, LinSolverCache
 from .nep import CDT, to_dev, to_host, stream_ptr
 
@@ -71,10 +72,6 @@ def nleigs(nep, *args, **kw):
         return run()
     with ctl.limit(limits=1, user_api="blas"):
         return run()
-
-
-class _OrthPassMiss(Exception):
-    pass
 
 
 nleigs.orth_misses = 0

@@ -20,10 +20,11 @@ import scipy.linalg as sla
 import torch
 
 from . import dense
+from ._ritzchecks import RitzChecks
 from .errmeasure import DefaultErrmeasure, estimate_errors
-from .exceptions import NoConvergenceException, LostOrthogonalityException
+from .exceptions import LostOrthogonalityException
 from .linsolvers import DefaultLinSolverCreator, create_linsolver
-from .nep import CDT, to_host, to_host_cm
+from .nep import CDT, to_host_cm
 
 EPS = np.finfo(float).eps
 
@@ -65,7 +66,6 @@ def tiar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
     tab = nep.derivative_table(sigma, m)
     z = torch.empty(n, dtype=CDT, device="cuda")
     conv_eig_hist = np.zeros(m + 1, dtype=int)
-    lam = np.zeros(0, dtype=np.complex128); QT = None; idx = np.zeros(0, dtype=int)
     # large sparse problems keep the Ritz block of a check column-major (tiled K2 with contiguous column loads)
     ritz_cm = bool(getattr(nep, "prefers_colmajor_ritz", lambda: False)())
     pnep = None
@@ -75,6 +75,7 @@ def tiar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
         if inner_solver_method is None:
             inner_solver_method = DefaultInnerSolver()
         err = np.full((m + 1, m + 4), np.nan)
+    checks = RitzChecks(m, tol, neigs, errhist, err)
     # neigs = Inf: no check can end the iteration, so the checks are DEFERRED -- eig(H_k) goes to a worker thread as soon as column k
     # of H exists (LAPACK runs without the GIL), Ritz block + residual batch of all steps are issued back to back behind the
     # recurrence with the host preparing check k + 1 while the device works on check k.  Same arithmetic, same history, same
@@ -88,22 +89,11 @@ def tiar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
         eig_pool = ThreadPoolExecutor(max_workers=2)
 
     def record_check(kk, laml, QTl, e):
-        nonlocal lam, QT, idx, conv_eig
-        ne = len(e)
-        idxl = np.argsort(e, kind="stable")
-        err[kk - 1, :ne] = e[idxl]
-        conv_eig = int(np.sum(e < tol))
-        if errhist is not None:
-            errhist.append(err[kk - 1, :ne].copy())
-        lam, QT, idx = laml, QTl, idxl
-        if kk == m or conv_eig >= neigs:
-            nrof = int(min(len(lam), neigs))
-            lam = lam[idx[:nrof]]
-            idx = idx[:nrof]
-        conv_eig_hist[kk - 1] = conv_eig
+        checks.record(kk, laml, QTl, e)
+        conv_eig_hist[kk - 1] = checks.conv_eig
 
-    k = 1; conv_eig = 0
-    while k <= m and conv_eig < neigs:
+    k = 1
+    while k <= m and checks.conv_eig < neigs:
         t0 = time.perf_counter()
         Bs = a[:k, k - 1, :k].T / np.arange(1, k + 1)[None, :]          # k x k, column j scaled by 1/(j+1)
         if fused:
@@ -161,18 +151,7 @@ def tiar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
             e = estimate_errors(errmeasure, lam, QT) if len(lam) else np.zeros(0)
             t7 = time.perf_counter()
             tm["host_eig"] += t5 - t4; tm["ritz"] += t6 - t5; tm["resid"] += t7 - t6
-            ne = len(e)
-            err[k - 1, :ne] = e
-            conv_eig = int(np.sum(e < tol))
-            idx = np.argsort(e, kind="stable")
-            err[k - 1, :ne] = e[idx]
-            if errhist is not None:
-                errhist.append(err[k - 1, :ne].copy())
-            if k == m or conv_eig >= neigs:
-                nrof = int(min(len(lam), neigs))
-                lam = lam[idx[:nrof]]
-                idx = idx[:nrof]
-            conv_eig_hist[k - 1] = conv_eig
+            record_check(k, lam, QT, e)
         k += 1
     k -= 1
     if defer:
@@ -191,15 +170,5 @@ def tiar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
         if prev is not None:
             record_check(prev[0], prev[1], prev[2], prev[3].get() if prev[3] is not None else np.zeros(0))
         eig_pool.shutdown(wait=False)
-    if conv_eig < neigs and neigs != np.inf:
-        Q = to_host(dense.rowmajor_to_cols(QT, idx[:len(lam)])) if QT is not None else None
-        msg = "Number of iterations exceeded. maxit=%d." % maxit
-        if conv_eig < 3:
-            msg += " Check that σ is not an eigenvalue."
-        raise NoConvergenceException(lam, Q, err[k - 1, :len(lam)], msg)
-    nc = min(len(lam), conv_eig)
-    lam = lam[:nc]
-    Qd = dense.rowmajor_to_cols(QT, idx[:nc])
-    if return_device:
-        return lam, Qd, Z[:k], conv_eig_hist
-    return lam, to_host_cm(Qd), Z[:k], conv_eig_hist
+    lam, Q = checks.finish(k, maxit, " Check that σ is not an eigenvalue.", None if return_device else to_host_cm)
+    return lam, Q, Z[:k], conv_eig_hist
