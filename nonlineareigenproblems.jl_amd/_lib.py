@@ -244,11 +244,7 @@ def require_gpu():
             _affinity.pin_to_gpu_numa(torch.cuda.current_device())
         except Exception:
             pass
-        import sys
-        wdir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_workers")
-        if wdir not in sys.path:
-            sys.path.insert(0, wdir)
-        import nep_amd_hostlu as _nep_hostlu               # big BLAS thread pools make the host side stall at random (see there)
+        from ._hostlu_pool import _nep_hostlu              # big BLAS thread pools make the host side stall at random (see there)
         _nep_hostlu.cap_blas_threads()
 
 

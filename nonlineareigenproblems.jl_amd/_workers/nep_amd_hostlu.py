@@ -174,7 +174,7 @@ def _store_order(Ac, permc_spec, symmetric, perm_c):
 
 def factor(data, indices, indptr, shape, permc_spec=None, diag_pivot_thresh=None, symmetric_mode=None, panel_size=8,
            relax=4, csr=False):
-    """UMFPACK-like strategy selection (see linsolvers.DeviceLU) + SuperLU factorisation.
+    """UMFPACK-like strategy selection (see _devicelu.DeviceLU) + SuperLU factorisation.
     panel_size / relax: SuperLU's panel width and relaxed-supernode size.  With single-threaded BLAS on these complex
     sparse matrices the defaults (20 / 10) are slower: measured on the bench host gun (n=9956) 20.4 -> 15.5 ms,
     waveguide n=91k 411 -> 348 ms, n=1e6 13.7 -> 13.5 s (scripts/diag/superlu_params.py); same fill, same pivots."""

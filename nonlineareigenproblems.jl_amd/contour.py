@@ -199,7 +199,7 @@ class _NodeSolve:
         if trace:
             import time as _t
             self._t0 = _t.perf_counter(); self._host_done = []; self._host_meta = []
-        # ---- all nodes on the GPU in one pass when the pattern has a device-factorisation plan (linsolvers._DeviceRefactor):
+        # ---- all nodes on the GPU in one pass when the pattern has a device-factorisation plan (_devicelu._DeviceRefactor):
         # one B x m_t by m_t x nnz product for the values, one batched numeric LU (every launch carries all nodes); nodes
         # whose factorisation is refused with the stored pivot sequence take the host path below
         self.ready = {}

@@ -263,9 +263,8 @@ def _iar_native_run(nep, M0inv, orthmethod, m, tol, neigs, errkind, sigma, gamma
     rc_ = M0inv.refine_coefficients() if M0inv.umfpack_refinements > 0 else None
     if M0inv.umfpack_refinements > 0 and rc_ is None:
         return None
-    hint = M0inv._recorded_plan if M0inv._recorded_plan is not None else M0inv._hint()
     o = IarOpts(m, int(check_error_every), dense._orth_code(orthmethod), int(max(0, M0inv.umfpack_refinements)), errkind[0],
-                -1 if hint is None else int(hint), float(tol), float(neigs), cdouble(sigma.real, sigma.imag), cdouble(gamma.real, gamma.imag))
+                -1, float(tol), float(neigs), cdouble(sigma.real, sigma.imag), cdouble(gamma.real, gamma.imag))
     res = IarResult()
 
     def fv_eval(ctx, nlam, lam_p, F_p):
@@ -286,16 +285,12 @@ def _iar_native_run(nep, M0inv, orthmethod, m, tol, neigs, errkind, sigma, gamma
     Qh = None if return_device else torch.empty((m, n), dtype=CDT, pin_memory=True)
     lam = np.zeros(m, dtype=np.complex128)
     err = np.full((m, m), np.nan, order="F")
-    st = lib.nep_iar_run(nep.dev.h, M0inv.lu.h, n, _C.addressof(o), hptr(v0), hptr(Ctab), mt,
-                         hptr(rc_[0]) if rc_ else None, hptr(rc_[1]) if rc_ else None, hptr(errkind[1]) if errkind[1] is not None else None,
-                         _C.cast(cb, c_vp), None, hptr(lam), c_vp(Qd.data_ptr()) if Qd is not None else None,
-                         c_vp(Qh.data_ptr()) if Qh is not None else None, hptr(err), c_vp(V.data_ptr()), _C.addressof(res), stream_ptr())
-    # what the run learnt about the refinement count belongs to this NEP and shift (FactorizeLinSolver._hint)
-    if res.refine_hint_off:
-        M0inv._note_hint(None)
-    elif res.refine_plan >= 0 and M0inv.umfpack_refinements > 0:
-        M0inv._recorded_plan = int(res.refine_plan)
-        M0inv._note_hint(int(res.refine_plan))
+    # (M0inv.refine puts the refinement count the run starts with into o.refine_hint and takes what the run learnt from res)
+    st = M0inv.refine.native_run(o, res, lambda: lib.nep_iar_run(
+        nep.dev.h, M0inv.lu.h, n, _C.addressof(o), hptr(v0), hptr(Ctab), mt,
+        hptr(rc_[0]) if rc_ else None, hptr(rc_[1]) if rc_ else None, hptr(errkind[1]) if errkind[1] is not None else None,
+        _C.cast(cb, c_vp), None, hptr(lam), c_vp(Qd.data_ptr()) if Qd is not None else None,
+        c_vp(Qh.data_ptr()) if Qh is not None else None, hptr(err), c_vp(V.data_ptr()), _C.addressof(res), stream_ptr()))
     if st == NEP_ERR_RETRY:
         if res.retry_reason == 1:
             raise _RefinementMiss(0)
@@ -307,7 +302,7 @@ def _iar_native_run(nep, M0inv, orthmethod, m, tol, neigs, errkind, sigma, gamma
     iar.native_runs += 1
     iar.last_route = "run"
     k = int(res.k); nret = int(res.nret)
-    M0inv.solves += k
+    M0inv.refine.solves += k
     if errhist is not None:
         for kc in range(1, k + 1):
             if kc % check_error_every == 0 or kc == m:

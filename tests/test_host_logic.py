@@ -413,60 +413,57 @@ def test_compute_Mder_union_pattern_with_stored_zeros_and_many_terms():
 
 
 def test_recorded_refinement_rule_replay():
-    """FactorizeLinSolver.review_recorded replays UMFPACK's stopping rule (the checked loop of solve_dev) on the omegas a
+    """Refine.review (behind FactorizeLinSolver.review_recorded) replays UMFPACK's stopping rule (the checked loop of solve_dev) on the omegas a
     native iar step records: accepted when the iterate kept is the one the rule returns (or at least as good), a miss when
     the rule would have continued or taken a worsening sweep back"""
-    from nep_amd.linsolvers import FactorizeLinSolver
+    from nep_amd.linsolvers import Refine
     eps = np.finfo(float).eps
-    s = FactorizeLinSolver.__new__(FactorizeLinSolver)
-    s.umfpack_refinements = 10; s._recorded_plan = None; s.last_omega = None
-    assert s.blind_plan_recorded() == 2                       # before any record: two sweeps
-    assert s.review_recorded(np.array([1e-13, 1e-16, 5e-17, 0.0]), 2)     # rule stops after 1 sweep, x_2 is as good
-    assert s._recorded_plan == 1 and s.blind_plan_recorded() == 1
-    assert s.review_recorded(np.array([1e-13, 1e-16, 0.0, 0.0]), 1)       # exactly what the rule does
-    assert s.review_recorded(np.array([1e-17, 0.0, 0.0, 0.0]), 0) and s._recorded_plan == 1   # never below one sweep
-    assert not s.review_recorded(np.array([1e-13, 0.0, 0.0, 0.0]), 0)     # omega_0 > 2 eps and no sweep taken: miss
-    assert not s.review_recorded(np.array([1e-9, 1e-12, 0.0, 0.0]), 1)    # still halving after the sweeps taken: miss
-    assert s.review_recorded(np.array([9.4e-11, 4.4885e-16, 0.0, 0.0]), 1)  # ... unless the kept iterate sits at the noise level of omega
-    assert s.review_recorded(np.array([1e-13, 8e-14, 0.0, 0.0]), 1)       # stagnation (> half): the rule stops there too
-    assert not s.review_recorded(np.array([1e-13, 5e-13, 0.0, 0.0]), 1)   # the sweep made it worse: rule takes it back
-    assert s.review_recorded(np.array([3e-16, 3.5e-16, 0.0, 0.0]), 1) == (3.5e-16 <= 4 * eps)   # ... unless at noise level
-    assert not s.review_recorded(np.array([1e-13, np.nan, 0.0, 0.0]), 1)
-    s.umfpack_refinements = 0
-    assert s.blind_plan_recorded() == 0
+    s = Refine(10)
+    assert s.plan() == 2                       # before any record: two sweeps
+    assert s.review(np.array([1e-13, 1e-16, 5e-17, 0.0]), 2)     # rule stops after 1 sweep, x_2 is as good
+    assert s.recorded == 1 and s.plan() == 1
+    assert s.review(np.array([1e-13, 1e-16, 0.0, 0.0]), 1)       # exactly what the rule does
+    assert s.review(np.array([1e-17, 0.0, 0.0, 0.0]), 0) and s.recorded == 1   # never below one sweep
+    assert not s.review(np.array([1e-13, 0.0, 0.0, 0.0]), 0)     # omega_0 > 2 eps and no sweep taken: miss
+    assert not s.review(np.array([1e-9, 1e-12, 0.0, 0.0]), 1)    # still halving after the sweeps taken: miss
+    assert s.review(np.array([9.4e-11, 4.4885e-16, 0.0, 0.0]), 1)  # ... unless the kept iterate sits at the noise level of omega
+    assert s.review(np.array([1e-13, 8e-14, 0.0, 0.0]), 1)       # stagnation (> half): the rule stops there too
+    assert not s.review(np.array([1e-13, 5e-13, 0.0, 0.0]), 1)   # the sweep made it worse: rule takes it back
+    assert s.review(np.array([3e-16, 3.5e-16, 0.0, 0.0]), 1) == (3.5e-16 <= 4 * eps)   # ... unless at noise level
+    assert not s.review(np.array([1e-13, np.nan, 0.0, 0.0]), 1)
+    s.umf = 0
+    assert s.plan() == 0
     # the settled count travels with the NEP object: the next solver of the same NEP starts with it, a miss withdraws it
     class _Nep: pass
     nep = _Nep()
-    a = FactorizeLinSolver.__new__(FactorizeLinSolver); a.umfpack_refinements = 10; a._recorded_plan = None; a.last_omega = None; a.nep = nep
-    assert a.blind_plan_recorded() == 2
-    assert a.review_recorded(np.array([1e-13, 1e-16, 5e-17, 0.0]), 2) and nep._refine_hint == 1
-    b = FactorizeLinSolver.__new__(FactorizeLinSolver); b.umfpack_refinements = 10; b._recorded_plan = None; b.last_omega = None; b.nep = nep
-    assert b.blind_plan_recorded() == 1
-    assert not b.review_recorded(np.array([1e-9, 1e-12, 0.0, 0.0]), 1) and nep._refine_hint is None
-    c = FactorizeLinSolver.__new__(FactorizeLinSolver); c.umfpack_refinements = 10; c._recorded_plan = None; c.last_omega = None; c.nep = nep
-    assert c.blind_plan_recorded() == 2
+    a = Refine(10, nep)
+    assert a.plan() == 2
+    assert a.review(np.array([1e-13, 1e-16, 5e-17, 0.0]), 2) and nep._refine_hint == 1
+    b = Refine(10, nep)
+    assert b.plan() == 1
+    assert not b.review(np.array([1e-9, 1e-12, 0.0, 0.0]), 1) and nep._refine_hint is None
+    c = Refine(10, nep)
+    assert c.plan() == 2
     # ... for good: a later clean record does not bring the hint back on this NEP object
-    assert c.review_recorded(np.array([1e-13, 1e-16, 5e-17, 0.0]), 2) and nep._refine_hint is None
-    d = FactorizeLinSolver.__new__(FactorizeLinSolver); d.umfpack_refinements = 10; d._recorded_plan = None; d.last_omega = None; d.nep = nep
-    assert d.blind_plan_recorded() == 2
+    assert c.review(np.array([1e-13, 1e-16, 5e-17, 0.0]), 2) and nep._refine_hint is None
+    d = Refine(10, nep)
+    assert d.plan() == 2
     # the hint belongs to ONE shift: a solver of the same NEP at another sigma neither starts with the count nor counts as settled
     nep2 = _Nep()
     def mk(lam):
-        x = FactorizeLinSolver.__new__(FactorizeLinSolver); x.umfpack_refinements = 10; x._recorded_plan = None; x.last_omega = None
-        x.nep = nep2; x.lam = lam
-        return x
+        return Refine(10, nep2, lam)
     e = mk(0.0)
-    assert not e.settled_plan()
-    assert e.review_recorded(np.array([1e-13, 1e-16, 5e-17, 0.0]), 2) and nep2._refine_hint == 1 and nep2._refine_hint_lam == 0j
-    assert mk(0.0).blind_plan_recorded() == 1 and mk(0.0).settled_plan()
-    assert mk(0.3 + 0.1j).blind_plan_recorded() == 2 and not mk(0.3 + 0.1j).settled_plan()
+    assert not e.settled()
+    assert e.review(np.array([1e-13, 1e-16, 5e-17, 0.0]), 2) and nep2._refine_hint == 1 and nep2._refine_hint_lam == 0j
+    assert mk(0.0).plan() == 1 and mk(0.0).settled()
+    assert mk(0.3 + 0.1j).plan() == 2 and not mk(0.3 + 0.1j).settled()
     # a step whose kept iterate was NOT recorded (7 of 8 once settled): the rule is replayed on x_0 .. x_{plan-1}
     f = mk(0.0)
-    assert f.review_recorded(np.array([1e-13, 0.0, 0.0, 0.0]), 1, final_recorded=False)            # still improving when the sweep was taken
-    assert f.review_recorded(np.array([1e-17, 0.0, 0.0, 0.0]), 1, final_recorded=False)            # x_0 converged already: accepted, not a miss
-    assert f._recorded_plan == 1 and nep2._refine_hint == 1
-    assert f.review_recorded(np.array([1e-13, 1e-17, 0.0, 0.0]), 2, final_recorded=False) and f._recorded_plan == 1
-    assert not f.review_recorded(np.array([1e-13, 9e-14, 0.0, 0.0]), 2, final_recorded=False)      # stagnation before the last sweep: miss
+    assert f.review(np.array([1e-13, 0.0, 0.0, 0.0]), 1, final_recorded=False)            # still improving when the sweep was taken
+    assert f.review(np.array([1e-17, 0.0, 0.0, 0.0]), 1, final_recorded=False)            # x_0 converged already: accepted, not a miss
+    assert f.recorded == 1 and nep2._refine_hint == 1
+    assert f.review(np.array([1e-13, 1e-17, 0.0, 0.0]), 2, final_recorded=False) and f.recorded == 1
+    assert not f.review(np.array([1e-13, 9e-14, 0.0, 0.0]), 2, final_recorded=False)      # stagnation before the last sweep: miss
     assert nep2._refine_hint is None
 
 
@@ -1117,12 +1114,12 @@ def test_julia_iar_tiar_methods_mirror_the_reference_keywords():
 
 
 def test_refinement_rule_in_c_equals_the_python_host():
-    """UMFPACK's stopping rule replayed on recorded omegas exists twice: linsolvers.py review_recorded (the step-at-a-time host) and
+    """UMFPACK's stopping rule replayed on recorded omegas exists twice: _refine.py Refine.review (the step-at-a-time host) and
     csrc/iar_run.hip (nep_iar_run; exported as nep_refine_review).  Same verdict, same planned sweeps, same hint on a grid of omega
     sequences around every threshold of the rule (no GPU needed)."""
     import itertools
     from nep_amd import _lib
-    from nep_amd.linsolvers import FactorizeLinSolver
+    from nep_amd.linsolvers import Refine
     eps = np.finfo(float).eps
     vals = [0.0, 0.5 * eps, 1.9 * eps, 2.1 * eps, 3.9 * eps, 4.1 * eps, 1e-14, 0.49e-14, 0.51e-14, 1e-12, 1e-9, float("nan"), float("inf")]
 
@@ -1135,16 +1132,97 @@ def test_refinement_rule_in_c_equals_the_python_host():
                 for w in itertools.product(vals, repeat=plan + 1):
                     if final is False and plan == 0:
                         continue
-                    s = FactorizeLinSolver.__new__(FactorizeLinSolver)
-                    s.umfpack_refinements = umf; s._recorded_plan = None; s.last_omega = None; s.lam = 0.0
-                    s.nep = _Nep()
+                    s = Refine(umf, _Nep(), 0.0)
                     w4 = np.zeros(4); w4[:plan + 1] = w
-                    ok = s.review_recorded(w4, plan, final_recorded=final)
+                    ok = s.review(w4, plan, final_recorded=final)
                     out = (_lib.c_i32 * 4)()
                     _lib.check(_lib.lib.nep_refine_review(umf, plan, 1 if final else 0, _lib.hptr(w4), -1, out))
                     hint = getattr(s.nep, "_refine_hint", None); off = getattr(s.nep, "_refine_hint_off", False)
                     assert bool(out[0]) == bool(ok), (umf, plan, final, w)
-                    assert out[1] == (-1 if s._recorded_plan is None else s._recorded_plan), (umf, plan, final, w, out[1], s._recorded_plan)
+                    assert out[1] == (-1 if s.recorded is None else s.recorded), (umf, plan, final, w, out[1], s.recorded)
                     assert out[2] == (-1 if hint is None else hint) and bool(out[3]) == bool(off), (umf, plan, final, w)
                     n += 1
     assert n > 10000
+
+
+def test_checked_refinement_loop_uses_the_rule_of_the_c_library():
+    """the checked loop of FactorizeLinSolver.solve_dev stops by _refine.rule_step, the C library's runs by struct Refine
+    (csrc/iar_run.hip, exported as nep_refine_review): the iterate the step function keeps on a whole omega sequence is the
+    one the C replay plans.  With plan = 3 >= umf the replay's "would go on" branch is unreachable, so this compares the
+    rule alone: every 4-tuple of the 13-value grid around the rule's thresholds, umf = 1, 2, 3 (85 683 sequences)."""
+    import itertools
+    from nep_amd import _lib
+    from nep_amd._refine import GO, TAKE_BACK, rule_step
+    eps = np.finfo(float).eps
+    vals = [0.0, 0.5 * eps, 1.9 * eps, 2.1 * eps, 3.9 * eps, 4.1 * eps, 1e-14, 0.49e-14, 0.51e-14, 1e-12, 1e-9, float("nan"), float("inf")]
+    w4 = np.zeros(4); pw = _lib.hptr(w4); out = (_lib.c_i32 * 4)()
+    review = _lib.lib.nep_refine_review
+    n = 0
+    for umf in (1, 2, 3):
+        for w in itertools.product(vals, repeat=4):
+            w_prev = np.inf
+            for step in range(4):
+                verdict = rule_step(w[step], w_prev, step, umf)
+                if verdict != GO:
+                    break
+                w_prev = w[step]
+            assert verdict != GO, (umf, w)                    # the rule ends after umf <= 3 sweeps
+            ret = step - 1 if verdict == TAKE_BACK else step
+            w4[:] = w
+            assert review(umf, 3, 1, pw, -1, out) == 0
+            assert max(ret, 1) == out[1], (umf, w, ret, out[1])
+            n += 1
+    assert n == 3 * 13 ** 4
+
+
+def test_linsolvers_is_the_facade_of_its_parts():
+    """every name that could be imported from nep_amd.linsolvers before the module was split still can, and is the object of
+    its new home; the unused blind_plan is gone"""
+    import nep_amd
+    from nep_amd import linsolvers as ls, _hostlu_pool, _devicelu, _refine, _gmres
+    homes = {_hostlu_pool: ("HostLUPool", "_nep_hostlu"),
+             _devicelu: ("DeviceLU", "_DeviceRefactor", "seed_plan_from_rank0"),
+             _refine: ("EPS", "Refine", "rule_step"),
+             _gmres: ("GMRESLinSolver", "GMRESLinSolverCreator")}
+    for mod, names in homes.items():
+        for name in names:
+            assert getattr(ls, name) is getattr(mod, name), name
+    for name in ("LinSolver", "FactorizeLinSolver", "BackslashLinSolver", "lin_solve", "LinSolverCreator", "FactorizeLinSolverCreator",
+                 "BackslashLinSolverCreator", "DefaultLinSolverCreator", "create_linsolver", "LinSolverCache", "DeflatedNEPLinSolver",
+                 "DeflatedNEPLinSolverCreator"):
+        assert getattr(ls, name).__module__ == "nep_amd.linsolvers", name
+    assert ls.DefaultLinSolverCreator is ls.FactorizeLinSolverCreator
+    assert nep_amd.DeviceLU is ls.DeviceLU
+    assert not hasattr(ls.FactorizeLinSolver, "blind_plan")
+
+
+def test_refine_bookkeeping_of_checked_solves():
+    """Refine.next_solve / checked_solve: once four consecutive checked solves agreed with the count p in force, solves are
+    taken on trust with p sweeps except every 8th, which is checked; a checked solve with another count puts that count in
+    force and starts the run again; with umfpack_refinements <= 0 nothing refines.  The count in force starts at 0, so for
+    p = 0 the first four checked solves are the run; for p > 0 the first checked solve puts p in force and the four after
+    it are the run (what FactorizeLinSolver.solve_dev has always done: a solver that needs sweeps checks its first five)."""
+    from nep_amd._refine import Refine
+    z = Refine(10)
+    for i in range(4):
+        assert z.next_solve() is None                         # solves 1-4: checked, no sweep needed
+        z.checked_solve(0, 1e-17)
+    assert [z.next_solve() for _ in range(3)] == [0, 0, 0]    # solves 5-7: blind, p = 0 sweeps
+    assert z.next_solve() is None                             # solve 8: checked
+    r = Refine(10)
+    for i in range(5):
+        assert r.next_solve() is None                         # solve 1 puts p = 2 in force, solves 2-5 agree with it
+        r.checked_solve(2, 1e-17)
+    assert [r.next_solve() for _ in range(2)] == [2, 2]       # solves 6-7: blind, p sweeps
+    assert r.next_solve() is None                             # solve 8: checked
+    r.checked_solve(2, 1e-17)
+    assert [r.next_solve() for _ in range(7)] == [2] * 7 and r.next_solve() is None        # 9-15 blind, 16 checked
+    assert r.solves == 16 and r.refine_checks == 6 and r.refine_steps_taken == 12 and r.last_omega == 1e-17
+    r.checked_solve(1, 3e-17)                                 # another count: the run starts again
+    for i in range(4):
+        assert r.next_solve() is None                         # solves 17-20
+        r.checked_solve(1, 3e-17)
+    assert r.next_solve() == 1                                # solve 21
+    for umf in (0, -1):
+        o = Refine(umf)
+        assert [o.next_solve() for _ in range(9)] == [0] * 9 and o.plan() == 0 and o.solves == 9 and o.refine_checks == 0
