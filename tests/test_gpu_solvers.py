@@ -856,13 +856,19 @@ def _gun_r1_setup(n):
     return Sigma, Xi, nodes, v
 
 
-def test_nleigs_basic_kat(na):
+# the orthogonalisation routes of nleigs: Gram-Schmidt enqueued with the DGKS decision on the device (default) and the
+# step-synchronous calls a run falls back to after an _OrthPassMiss
+NLEIGS_ORTH_ROUTES = pytest.mark.parametrize("route", [{}, {"_sync_orth": True}], ids=["default", "sync_orth"])
+
+
+@NLEIGS_ORTH_ROUTES
+def test_nleigs_basic_kat(na, route):
     # test/nleigs/nleigs_basic.jl:11-19,42-47 ; src/method_nleigs.jl:44-50
     from oracle import neps as oneps, nleigs as onl, gallery as og
     B = [np.array([[1., 3], [5, 6]]), np.array([[3., 4], [6, 6]]), np.eye(2)]
     Sigma = np.array([-10 - 2j, 10 - 2j, 10 + 2j, -10 + 2j])
     info = {}
-    lam, X, res = na.nleigs(na.PEP(B), Sigma, maxit=10, v=np.ones(2) + 0j, blksize=5, info=info)
+    lam, X, res = na.nleigs(na.PEP(B), Sigma, maxit=10, v=np.ones(2) + 0j, blksize=5, info=info, **route)
     lo, Xo, ro = onl.nleigs(oneps.PEP(B), Sigma, maxit=10, v=np.ones(2) + 0j, blksize=5)
     assert len(lam) == 4 and len(lo) == 4
     _match(lam, lo, 1e-9)
@@ -870,10 +876,10 @@ def test_nleigs_basic_kat(na):
     assert max(np.linalg.norm(o.compute_Mlincomb(lam[i], X[:, i])) for i in range(4)) < 1e-5
     assert info["kconv"] == 6 and info["nfact"] == 4
     cB = [b + 1j * np.eye(2) for b in B]
-    lam, X, res = na.nleigs(na.PEP(cB), Sigma, maxit=10, v=np.ones(2) + 0j, blksize=5)
+    lam, X, res = na.nleigs(na.PEP(cB), Sigma, maxit=10, v=np.ones(2) + 0j, blksize=5, **route)
     assert len(lam) == 3
     d = na.nep_gallery("dep0"); od = og.dep0()
-    lam, X, res = na.nleigs(d, np.array([1 + 1j, 1 - 1j, -1 - 1j, -1 + 1j]), v=np.ones(5) + 0j)
+    lam, X, res = na.nleigs(d, np.array([1 + 1j, 1 - 1j, -1 - 1j, -1 + 1j]), v=np.ones(5) + 0j, **route)
     assert len(lam) >= 2
     assert max(np.linalg.norm(od.compute_Mlincomb(lam[i], X[:, i])) for i in range(len(lam))) < 1e-10
 
@@ -917,38 +923,43 @@ def test_nleigs_nep_types(na):
         _match(lam, ref, 1e-9)
 
 
-def test_nleigs_static_and_details_vs_oracle(na):
+@NLEIGS_ORTH_ROUTES
+def test_nleigs_static_and_details_vs_oracle(na, route):
     """test/nleigs/nleigs_basic.jl:28-73 on the device path: static variant (warning + 4 eigenvalues), return_details
-    (0 / 3 / 4 eigenvalues, history consistent with the returned values); each case against the oracle (1e-9); then the
-    static variant on a sparse gun twin against the oracle."""
+    (0 / 3 / 4 eigenvalues, history consistent with the returned values); each case against the oracle (1e-9)."""
     import warnings
-    from oracle import nleigs as onl, neps as oneps, gallery as og
+    from oracle import nleigs as onl, neps as oneps
     B = [np.array([[1.0, 3], [5, 6]]), np.array([[3.0, 4], [6, 6]]), np.eye(2)]
     Sig = [-10.0 - 2j, 10 - 2j, 10 + 2j, -10 + 2j]
     pep = na.PEP(B); opep = oneps.PEP(B)
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")
-        lam, X, _ = na.nleigs(pep, Sig, maxit=10, v=np.ones(2) + 0j, maxdgr=5, blksize=5, static=True)
+        lam, X, _ = na.nleigs(pep, Sig, maxit=10, v=np.ones(2) + 0j, maxdgr=5, blksize=5, static=True, **route)
         assert any("Linearization not converged" in str(x.message) for x in w)
     lo, Xo, _ = onl.nleigs(opep, Sig, maxit=10, v=np.ones(2) + 0j, maxdgr=5, blksize=5, static=True)
     assert len(lam) == 4
     _match(lam, lo, 1e-9)
     with warnings.catch_warnings(record=True):
         warnings.simplefilter("always")
-        lam, X, _, d = na.nleigs(pep, Sig, maxit=5, v=np.ones(2) + 0j, blksize=5, return_details=True)
+        lam, X, _, d = na.nleigs(pep, Sig, maxit=5, v=np.ones(2) + 0j, blksize=5, return_details=True, **route)
     assert len(lam) == 0
     Bc = [b + 1j * np.eye(2) for b in B]
-    lam, X, _, d = na.nleigs(na.PEP(Bc), Sig, maxit=10, v=np.ones(2) + 0j, blksize=5, return_details=True)
+    lam, X, _, d = na.nleigs(na.PEP(Bc), Sig, maxit=10, v=np.ones(2) + 0j, blksize=5, return_details=True, **route)
     lo, Xo, _, do = onl.nleigs(oneps.PEP(Bc), Sig, maxit=10, v=np.ones(2) + 0j, blksize=5, return_details=True)
     assert len(lam) == 3
     _match(lam, lo, 1e-9)
-    lam, X, res, d = na.nleigs(pep, Sig, maxit=10, v=np.ones(2) + 0j, blksize=5, return_details=True)
+    lam, X, res, d = na.nleigs(pep, Sig, maxit=10, v=np.ones(2) + 0j, blksize=5, return_details=True, **route)
     lo, Xo, reso, do = onl.nleigs(opep, Sig, maxit=10, v=np.ones(2) + 0j, blksize=5, return_details=True)
     assert len(lam) == 4 and d.Lam.shape == do.Lam.shape and d.kconv == do.kconv
     l2 = d.Lam[:, -1]; r2 = d.Res[:, -1]
     conv = (r2 < 1e-12) & onl.in_Sigma(l2, np.asarray(Sig, dtype=complex), 0)
     assert conv.sum() == 4 and len(set(np.round(np.concatenate([lam, l2[conv]]), 8))) == 4
-    # static variant on a sparse gun twin (leja nodes in both phases are replaced by given nodes: variant S set-up)
+
+
+def test_nleigs_static_gun_twin_vs_oracle(na):
+    """static variant on a sparse gun twin (leja nodes in both phases are replaced by given nodes: variant S set-up) against
+    the oracle"""
+    from oracle import nleigs as onl, gallery as og
     n = 400
     onep = og.nlevp_native_gun(n); nep = na.nep_gallery("nlevp_native_gun", n)
     gam, mu = 300.0 ** 2 - 200.0 ** 2, 250.0 ** 2
@@ -1078,7 +1089,8 @@ def test_nleigs_first_call_seeds_the_device_plan(na):
     _match(l2, l1, 1e-8)
 
 
-def test_nleigs_lowrank_degree2_vs_oracle(na):
+@NLEIGS_ORTH_ROUTES
+def test_nleigs_lowrank_degree2_vs_oracle(na, route):
     """polynomial part of degree 2 + two low-rank exponential terms: the n-row recurrences of blocks 1..p-1, the UU^H seams
     at block p and the corrected first-block-row term (oracle/nleigs.py backslash) on the device; dynamic and static
     variants against the oracle (1e-8) and against the full-block device run"""
@@ -1098,7 +1110,7 @@ def test_nleigs_lowrank_degree2_vs_oracle(na):
         ref, _, _ = na.nleigs(full, Sigma, maxit=60, v=np.ones(n) + 0j)
         assert len(ref) == 8
         for static in (False, True):
-            lam, X, res = na.nleigs(lowr, Sigma, maxit=60, v=np.ones(n) + 0j, static=static)
+            lam, X, res = na.nleigs(lowr, Sigma, maxit=60, v=np.ones(n) + 0j, static=static, **route)
             lo, Xo, ro = onl.nleigs(olr, Sigma, maxit=60, v=np.ones(n) + 0j, static=static)
             _match(lam, lo, 1e-8)
             _match(lam, ref, 1e-7)
