@@ -747,6 +747,48 @@ int32_t nep_iar_wait(nep_iar* s, int32_t k);
  * complete (the eigen-decomposition of step k on a second stream: nep_hess_eigvals_dev on row block dH of nep_iar_create) */
 int32_t nep_iar_stream_wait(nep_iar* s, int32_t k, nep_stream stream);
 
+/* ---- a shift-and-invert Krylov-Schur eigensolver for a linear pencil A x = d B x (csrc/lineig.hip) ------------------------
+ * K13  in-place basis rotation, the compression step of a Krylov-Schur restart:
+ *   V[:, 0:p] <- V[:, 0:m] Q;   carry != 0: V[:, p] <- V[:, m]  (the residual vector v_{m+1} moves next to the kept block)
+ * replaces: the basis update of ArnoldiMethod.jl's restart behind `partialschur(..., which=LM())`, src/LinSolvers.jl:409 (an
+ *           out-of-place product V[:, 1:m] * Q[:, 1:p] and a copy back there; composed from nep_gemm_ts it would need a second
+ *           rows x p block).
+ * dV: rows x (m + 1) column-major device block (ldv); hQ: m x p complex column-major HOST table (ldq) that may be freed or
+ * overwritten on return (staged through a pinned ring into a device slot that is not handed out again before the kernel that
+ * reads it has finished: calls may follow each other at once).  Rows >= `rows` of a column, the padding between rows and ldv
+ * and the columns > m are neither read nor written; column m is read only with carry; the columns p + (carry != 0) .. m - 1
+ * are left unspecified.  Asynchronous; ONE launch, no scratch of the size of the basis, no atomics, fixed summation order (k
+ * ascending): two calls on equal inputs give the same bits.  Bytes moved: 16 rows (m + p).
+ * NEP_ERR_ARG (nothing launched, V unchanged) for a NULL dV / hQ, rows < 1, m < 1, p < 1, p > m, ldv < rows, ldq < m;
+ * NEP_ERR_UNSUPPORTED (nothing launched) for m > 128. */
+int32_t nep_basis_rotate(nep_cdouble* dV, int64_t ldv, int64_t rows, int32_t m, int32_t p, const nep_cdouble* hQ, int64_t ldq,
+                         int32_t carry, nep_stream stream);
+
+/* Arnoldi expansion for the operator C^-1 B of a pencil carried as an SPMF handle plus coefficient rows, B = sum_t cB_t A_t,
+ * C = tau B - A = sum_t (tau cB_t - cA_t) A_t factorised by the caller (any nep_lu handle).
+ * replaces: the shift-and-invert operator x -> Cfact \ (B x) of inner_eigs_solve, src/LinSolvers.jl:390-416, expanded by
+ *           ArnoldiMethod.jl there; its caller is the loop of the method of successive linear problems, src/method_mslp.jl:61-70.
+ * Step j (0-based): w = sum_t cB_t A_t v_j (nep_mlincomb_dev), w <- C^-1 w (nep_lu_solve), DGKS or CGS of w against
+ * V[:, 0..j] (nep_orth_dev without an active-row table), w / beta to column j + 1, and row j of the device coefficient block dS
+ * (maxdim rows of maxdim + 4 complex: the j + 1 projection coefficients -- a full column, not a Hessenberg one: after a restart
+ * the kept block is not Hessenberg --, then (beta, 0), then the flag word (passes, 2 breakdown + another_pass_wanted)) is copied
+ * to the caller's PINNED host block of the same layout behind an event.  The flag word is the one of nep_orth_dev, unchanged.  A
+ * new vector inside span(V) is reported through it only: breakdown is set when beta is not a positive finite number, and
+ * another_pass_wanted when the last DGKS pass still asked for another one (the vector lies in span(V) to working precision:
+ * "twice is enough"), so a DGKS step with a non-zero second component of its flag word has found an invariant subspace.  Later
+ * columns of the same call are then unspecified but every call returns NEP_OK.
+ * dV: n x (maxdim + 1) column-major (ldv >= n), column 0 = the normalised start vector; d_cB: the mt coefficients of B on the
+ * device; dwork_n: n complex of scratch; orth_method: 0 DGKS, 1 CGS.  nep_arnoldi_steps enqueues steps j0 .. j0 + count - 1 and
+ * waits for nothing; nep_arnoldi_wait blocks until row j has arrived.  NEP_ERR_ARG for a NULL argument, n < 1, maxdim < 1,
+ * ldv < n, steps outside 0 .. maxdim - 1, a wait for a step that was never enqueued. */
+typedef struct nep_arnoldi nep_arnoldi;
+int32_t nep_arnoldi_create(nep_spmf* spmf, nep_lu* lu, int64_t n, int32_t maxdim, nep_cdouble* dV, int64_t ldv,
+                           const nep_cdouble* d_cB, nep_cdouble* dwork_n, nep_cdouble* dS, nep_cdouble* h_pinnedS,
+                           int32_t orth_method, nep_arnoldi** out);
+int32_t nep_arnoldi_destroy(nep_arnoldi* s);
+int32_t nep_arnoldi_steps(nep_arnoldi* s, int32_t j0, int32_t count, nep_stream stream);
+int32_t nep_arnoldi_wait(nep_arnoldi* s, int32_t j);
+
 /* ---- the whole infinite-Arnoldi run as one call ---------------------------------------------
  * replaces: the body of `iar(::Type{T}, nep::NEP; orthmethod, maxit, linsolvercreator, tol, neigs, errmeasure, sigma, gamma, v, logger,
  *           check_error_every, ...)`, src/method_iar.jl:46-182, after `create_linsolver` (:84): recurrence (:94-109, nep_iar_step),

@@ -35,6 +35,8 @@ from .nleigs import nleigs, NleigsSolutionDetails
 from .aaaeigs import AAAeigs, svAAA, AAASolutionDetails
 from .broyden import broyden, broyden_T
 from .blocknewton import blocknewton
+from .eigsolvers import EigSolver, EigenEigSolver, ArnoldiEigSolver, DefaultEigSolver, eig_solve
+from .mslp import mslp
 from . import rk_helper
 from .contour import (contour_beyn, contour_block_SS, integrate_interval, MatrixIntegrator, MatrixTrapezoidal,
                       MatrixTrapezoidalSharded, probe_block)

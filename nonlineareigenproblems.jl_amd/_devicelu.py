@@ -420,6 +420,35 @@ def lu_from_terms(nep, lam, permc_spec, lu_kw):
     return lu
 
 
+def lu_from_term_coeffs(nep, coef, lu_kw=None):
+    """sibling of lu_from_terms for a matrix given by its coefficient row, C = sum_t coef[t] A_t on the terms of a pure SPMF NEP
+    (the shifted pencil tau M'(lam) - M(lam) of an eigensolver: coef = tau f_t'(lam) - f_t(lam)): assembled and factorised on the
+    device with the stored pivot sequence of the pattern's plan.  None: no plan (yet), a NEP with terms outside its SPMF sum, a
+    refusal -- the caller takes the general route."""
+    lu_kw = lu_kw or {}
+    if set(lu_kw) - {"expected_solves"} or not _DeviceRefactor.enabled() or env_str("NEP_LU_TERMS", "1") == "0":
+        return None
+    from .nep import AbstractSPMF
+    if not (isinstance(nep, AbstractSPMF) and type(nep).compute_Mder is AbstractSPMF.compute_Mder
+            and hasattr(nep, "aligned_terms_dev")):
+        return None
+    if not _DeviceRefactor.plans:
+        return None
+    al = nep.aligned_terms_dev()
+    if al is None:
+        return None
+    indptr, indices, D_dev, G = al
+    plan = _DeviceRefactor.lookup(_DeviceRefactor.key(_Pattern(indptr, indices, (nep.n, nep.n)), (None, None, None)))
+    if plan is None:
+        return None
+    Cf = np.asarray(coef, dtype=np.complex128).reshape(1, -1)
+    normA = np.sqrt(np.maximum(np.einsum("bs,st,bt->b", Cf.conj(), G, Cf).real, 0.0))
+    lu = _DeviceRefactor.factor_batch_terms(plan, nep.n, D_dev, Cf, normA, expected_solves=int(reused(lu_kw)["expected_solves"]))[0]
+    if lu is not None:
+        lu.strategy = dict(plan["strategy"], numeric="device (stored pivot sequence)")
+    return lu
+
+
 def seed_plan_from_rank0(nep, lam, group=None, permc_spec=None, wait=True):
     """Collective over the ranks of a node (torch.distributed): the FIRST factorisation of a sparsity pattern -- the host SuperLU
     run that fixes ordering, pivot sequence and fill, and from which the pattern's device-factorisation plan is built -- is done

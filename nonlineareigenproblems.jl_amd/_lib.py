@@ -172,6 +172,11 @@ SIGNATURES = {
     "nep_iar_steps": [c_vp, c_i32, c_i32, c_i32, c_vp],
     "nep_iar_wait": [c_vp, c_i32],
     "nep_iar_stream_wait": [c_vp, c_i32, c_vp],
+    "nep_basis_rotate": [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_i64, c_i32, c_vp],
+    "nep_arnoldi_create": [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, P(c_vp)],
+    "nep_arnoldi_destroy": [c_vp],
+    "nep_arnoldi_steps": [c_vp, c_i32, c_i32, c_vp],
+    "nep_arnoldi_wait": [c_vp, c_i32],
     "nep_devprim_exclusive_sum": [c_vp, c_vp, c_i64, c_vp],
     "nep_devprim_sort_pairs": [c_vp, c_vp, c_i64, c_i32, c_vp],
     "nep_refine_review": [c_i32, c_i32, c_i32, c_vp, c_i32, c_vp],

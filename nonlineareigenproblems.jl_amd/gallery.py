@@ -254,6 +254,34 @@ def dep0_sparse(n=100, p=0.25):
 GALLERY["dep0_sparse"] = dep0_sparse
 
 
+def dep_double():
+    """src/gallery_extra/gallery_examples.jl:35-49: 3 x 3 DEP in companion form with a double, non-semisimple eigenvalue at
+    3 pi i (E. Jarlebring, Convergence factors of Newton methods for nonlinear eigenvalue problems, LAA 2012), tau = 1"""
+    pi = np.pi
+    den = 8 + 5 * pi
+    a = [2 / 5 * (65 * pi + 32) / den, 9 * pi ** 2 * (13 + 5 * pi) / den, 324 / 5 * pi ** 2 * (5 * pi + 4) / den]
+    b = [(260 * pi + 128 + 225 * pi ** 2) / (10 * den), 45 * pi ** 2 / den, 81 * pi ** 2 * (40 * pi + 32 + 25 * pi ** 2) / (10 * den)]
+    A0 = np.array([[0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [-a[2], -a[1], -a[0]]])
+    A1 = np.array([[0.0, 0.0, 0.0], [0.0, 0.0, 0.0], [-b[2], -b[1], -b[0]]])
+    return DEP([A0, A1], [0.0, 1.0])
+
+
+GALLERY["dep_double"] = dep_double
+
+
+def beam(n=100):
+    """src/gallery_extra/gallery_examples.jl:143-152: sparse DEP modelling a beam, h = 1 / n: A0 = tridiag(1, -2, 1) with the last
+    row replaced by (.., -1 / h, 1 / h), A1 = e_n e_n^T, tau = 1"""
+    A0 = sp.lil_matrix(sp.diags([np.ones(n - 1), -2.0 * np.ones(n), np.ones(n - 1)], [-1, 0, 1], shape=(n, n)))
+    A0[n - 1, n - 1] = float(n)
+    A0[n - 1, n - 2] = -float(n)
+    A1 = sp.csc_matrix(([1.0], ([n - 1], [n - 1])), shape=(n, n))
+    return DEP([sp.csc_matrix(A0), A1], [0.0, 1.0])
+
+
+GALLERY["beam"] = beam
+
+
 def particle_nep(interval):
     """The "particle in a canyon" problem of test/nleigs/particle_test_utils.jl:37-165 (after W. Vandenberghe): a 2-D
     Schroedinger operator H - lam I on a 201 x 81 grid plus, per branch point (eigenvalue of the lead Hamiltonian), a

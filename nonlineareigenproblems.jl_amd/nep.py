@@ -190,6 +190,18 @@ class SPMFDevice:
         assert Fm.shape == (self.mt, k)
         check(lib.nep_resid_batch_dev(self.h, k, hptr(Fm), c_vp(QT.data_ptr()), ldq, c_vp(out_dev.data_ptr()), stream_ptr()))
 
+    def resid_batch_async(self, F, QT):
+        """enqueues K2 for the k columns of the row-major block QT with the coefficient columns F (mt x k) and the copy of the
+        squared norms to pinned memory; returns a PendingNorms (the one place that knows the panel layout of the output)"""
+        k = F.shape[1]
+        out = torch.empty(2 * k, dtype=torch.float64, device="cuda")
+        self.resid_batch_dev(F, QT, k, QT.shape[1], out)
+        pin = torch.empty(2 * k, dtype=torch.float64, pin_memory=True)
+        pin.copy_(out, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return PendingNorms(pin=pin, ev=ev, k=k, F=F, keep=(out, QT), panel=min(256, max(1, 3072 // self.mt)))
+
     def resid_batch_cm(self, F, Qc, k, row0=-1, tail=None):
         """K2 with a column-major block Qc (device (k, n) tensor): squared norms as a device tensor of 2k doubles (no
         synchronisation); row0 >= 0: rows below it in the norms, the rows from it on written to `tail` (device (k, n - row0))"""
@@ -614,13 +626,7 @@ class AbstractSPMF(NEP):
         F = np.empty((len(fv), k), dtype=np.complex128, order="F")
         for i, f in enumerate(fv):
             F[i, :] = f.values(la)
-        out = torch.empty(2 * k, dtype=torch.float64, device="cuda")
-        self.dev.resid_batch_dev(F, QT, k, QT.shape[1], out)
-        pin = torch.empty(2 * k, dtype=torch.float64, pin_memory=True)
-        pin.copy_(out, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return PendingNorms(pin=pin, ev=ev, k=k, F=F, keep=(out, QT), panel=min(256, max(1, 3072 // len(fv))))
+        return self.dev.resid_batch_async(F, QT)
 
     def fro_norms(self):
         if self._fro is None:
