@@ -738,7 +738,13 @@ int32_t nep_iar_create(nep_spmf* spmf, nep_lu* lu, int64_t n, int32_t m, nep_cdo
                        int32_t orth_method, nep_iar** out);
 int32_t nep_iar_destroy(nep_iar* s);
 /* refine_steps | 0x100: the backward error of the KEPT iterate is recorded only in steps whose index is a multiple of 8 (its slot
- * stays 0 otherwise) -- for callers whose refinement count has settled (the check costs one pass over the matrices per step) */
+ * stays 0 otherwise) -- for callers whose refinement count has settled (the check costs one pass over the matrices per step).
+ * What step k writes: rows 0 .. (k+1)n - 1 of column k of dV; row k-1 of dH and of the pinned block (entries 0 .. k+3, nothing
+ * behind them); and, on the fused path only (mt <= 4 and NEP_IAR_FUSE_VC not 0 when the object was created) and only for k < m,
+ * the shifted blocks of column k+1, rows n .. (k+2)n - 1 = column k divided blockwise by 1 .. k+1, which step k+1 then uses as
+ * they are (together with a coefficient product the object keeps for it).  Rows 0 .. n-1 of column k+1, every later column,
+ * the padding between n(m+1) and ldv and the columns < k are not written.  A caller that edits column k between step k and
+ * step k+1 (a restart, a re-orthogonalisation of its own) must create a new object: the hand-over would be stale. */
 int32_t nep_iar_step(nep_iar* s, int32_t k, int32_t refine_steps, nep_stream stream);
 /* steps k0 .. k0+count-1 (same refine_steps) in one foreign call */
 int32_t nep_iar_steps(nep_iar* s, int32_t k0, int32_t count, int32_t refine_steps, nep_stream stream);
