@@ -241,6 +241,25 @@ int32_t nep_cork_expand(int32_t r, int32_t k, int32_t c, const nep_cdouble* dU, 
                         const nep_cdouble* du, const nep_cdouble* dg, nep_cdouble alpha, nep_cdouble* dOut, int64_t ldo,
                         nep_stream stream);
 
+/* Interpolation coefficients of a sampled matrix function, entry by entry:
+ *   C[r(e), i] = beta C[r(e), i] + sum_{j < J} W[i, j] F[e, j],   e < E, i < K,   r(e) = dpos ? dpos[e] : e.
+ * replaces: src/types_cheb_pep.jl:94-114 (chebyshev_compute_coefficients: Ck = map(i -> sum(Fk .* Tmat[i,:]), 1:k), k sparse
+ *           matrix sums per coefficient) and src/types_poly.jl:121-164 (interpolate: one Vandermonde solve per non-zero, or the
+ *           Kronecker-product solves of the dense branch).  W is the weight table Tmat, the inverse Vandermonde matrix, or either
+ *           of them times the function values of the terms of an SPMF at the nodes (then F is the term block D itself).
+ * dF: E rows of J contiguous values, row stride ldf >= J (entry-major: the layout of the aligned term block of an SPMF),
+ * complex128 when f_is_complex != 0, float64 otherwise.  hW: K x J column-major HOST table (hW[i + j K]; may be freed on return,
+ * staged by the call).  dpos: E device int32 row numbers of dC or NULL; the caller guarantees that they are distinct and inside
+ * dC.  dC: rows of K contiguous complex128 values, row stride ldc >= K.  beta is 0 or 1; with 0 dC is never read.  dC must not
+ * overlap dF (checked when dpos is NULL).  Entries >= E, the padding of a row of dF or dC and rows of dC that dpos does not name
+ * are neither read nor written.  Asynchronous; ONE launch, every value of dF is read once, no atomics, fixed summation order
+ * (the old value, then j ascending): two calls give the same bits.  E = 0 is a no-op.
+ * NEP_ERR_UNSUPPORTED (nothing launched, nothing written) unless 1 <= J <= 64 and 1 <= K <= 64; NEP_ERR_ARG (nothing launched)
+ * for E < 0, ldf < J, ldc < K, beta outside {0, 1}, a NULL hW, a NULL dF / dC with E > 0, or dC overlapping dF without a map. */
+int32_t nep_interp_coeffs(int64_t E, int32_t J, int32_t K, const void* dF, int64_t ldf, int32_t f_is_complex,
+                          const nep_cdouble* hW, const int32_t* dpos, int32_t beta, nep_cdouble* dC, int64_t ldc,
+                          nep_stream stream);
+
 /* One pass over the approximate inverse Jacobian T of Broyden's method (n x n, column-major, ldt, device):
  *   T[i, j] += u0[i] a0[j]                     when du0 / da0 are given: the only write to T
  *   y[i]     = sum_j T_new[i, j] x[j]          when dx / dy are given

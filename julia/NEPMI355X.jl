@@ -502,6 +502,11 @@ zgemm!(C::DevBuf, ta, tb, α, A::DevBuf, B::DevBuf, β) =
 gemv_hd!(y::DevBuf, A::DevBuf, x::DevBuf, d::Union{DevBuf,Nothing}) =
     chk(ccall((:nep_gemv_hd, LIB), Cint, (Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
               A.ptr, A.rows, A.rows, A.cols, x.ptr, d === nothing ? C_NULL : d.ptr, y.ptr, C_NULL))
+# C[:, e] = β C[:, e] + W F[:, e] for every column e of F (one column per matrix entry, its J samples or term values): the
+# coefficients of ChebPEP (types_cheb_pep.jl:94-114, W = Tmat) and interpolate (types_poly.jl:121-164, W = inv(V)); W is K x J
+interp_coeffs!(C::DevBuf, W::Matrix{ComplexF64}, F::DevBuf, β::Integer = 0) =
+    chk(ccall((:nep_interp_coeffs, LIB), Cint, (Int64, Int32, Int32, Ptr{Cvoid}, Int64, Int32, Ptr{ComplexF64}, Ptr{Cvoid}, Int32,
+              Ptr{Cvoid}, Int64, Ptr{Cvoid}), F.cols, F.rows, C.rows, F.ptr, F.rows, 1, W, C_NULL, β, C.ptr, C.rows, C_NULL))
 
 # ---- quadrature seam (src/method_contour_common.jl:46,61-94): nodes sharded over ranks, RCCL all-gather ------
 # One Julia process per GPU (e.g. `mpiexec -n 8 julia ...` with MPI.jl only as the launcher / unique-id carrier).

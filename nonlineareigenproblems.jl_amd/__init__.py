@@ -9,8 +9,8 @@ from . import _lib, funcs, dense
 from ._lib import NepError, device_count, LIB_PATH
 from .exceptions import NoConvergenceException, LostOrthogonalityException
 from .nep import (NEP, AbstractSPMF, SPMF_NEP, DEP, PEP, SumNEP, DerSPMF, shift_and_scale, SPMFDevice, Mder_NEP,
-                  LowRankMatrixAndFunction, LowRankFactorizedNEP,
-                  to_dev, to_host)
+                  LowRankMatrixAndFunction, LowRankFactorizedNEP, ChebPEP, interpolate, chebyshev_nodes, chebyshev_weights,
+                  interp_coeffs, to_dev, to_host)
 from .linsolvers import (LinSolver, FactorizeLinSolver, BackslashLinSolver, FactorizeLinSolverCreator,
                          BackslashLinSolverCreator, DefaultLinSolverCreator, create_linsolver, lin_solve,
                          LinSolverCache, DeviceLU, HostLUPool, GMRESLinSolver, GMRESLinSolverCreator, seed_plan_from_rank0,
@@ -30,7 +30,7 @@ from .infbilanczos import infbilanczos, left_right_scalar_prod
 from .deflation import (deflate_eigpair, get_deflated_eigpairs, normalize_schur_pair, verify_deflate_mode, DeflatedNEPMM,
                         DeflatedGenericNEP, DeflatedSPMF)
 from .projection import (Proj_SPMF_NEP, create_proj_NEP, inner_solve, InnerSolver, DefaultInnerSolver, IARInnerSolver,
-                         NewtonInnerSolver, IARChebInnerSolver, PolyeigInnerSolver, polyeig)
+                         NewtonInnerSolver, IARChebInnerSolver, PolyeigInnerSolver, polyeig, companion, colleague_pencil)
 from .nleigs import nleigs, NleigsSolutionDetails
 from .aaaeigs import AAAeigs, svAAA, AAASolutionDetails
 from .broyden import broyden, broyden_T

@@ -329,6 +329,78 @@ class WEPSqrt(ScalarFun):
         raise NotImplementedError("WEPSqrt.matfun (compute_MM with non-diagonal S) is not supported")
 
 
+class Chebyshev(ScalarFun):
+    """T_j(x), x = 2 (lam - a) / (b - a) - 1: the Chebyshev polynomial of the first kind scaled to [a, b], the basis of ChebPEP
+    (src/types_cheb_pep.jl:24-58).  Everything goes through T_{i+1} = 2 x T_i - T_{i-1}, which holds for complex lam, for lam
+    outside [a, b] and for matrices alike; the reference's cos(j acos x) needs a work-around to stay real on real matrices
+    (types_cheb_pep.jl:11-23) and leaves the reals for |x| > 1.  Applied to the polynomials h -> T_i(x + c h), c = 2 scale / (b - a),
+    as coefficient vectors in h, the same recurrence gives the Taylor coefficients in closed form (no Jordan block): the entries of
+    order > j are exact zeros."""
+
+    def __init__(self, j, a=-1.0, b=1.0):
+        if np.iscomplexobj(a) or np.iscomplexobj(b) or not float(a) < float(b):
+            raise ValueError("Chebyshev: the interval [a, b] needs real a < b")
+        if int(j) != j or j < 0:
+            raise ValueError("Chebyshev: the degree must be a non-negative integer")
+        self.j, self.a, self.b = int(j), float(a), float(b)
+
+    def real_on_reals(self):
+        return True
+
+    def _x(self, lam):
+        return 2.0 * (lam - self.a) / (self.b - self.a) - 1.0
+
+    def values(self, lams):
+        x = self._x(np.asarray(lams, dtype=np.complex128))
+        t0, t1 = np.ones_like(x), x
+        if self.j == 0:
+            return t0
+        for _ in range(self.j - 1):
+            t0, t1 = t1, 2.0 * x * t1 - t0
+        return t1
+
+    def __call__(self, lam):
+        return complex(self.values(np.array([lam]))[0])
+
+    def taylor(self, lam, k, scale=1.0):
+        x = complex(self._x(complex(lam)))
+        c = 2.0 * scale / (self.b - self.a)                  # chain factor of h -> x + c h
+        m = self.j + 1
+        p0 = np.zeros(m, dtype=np.complex128); p0[0] = 1.0   # T_0
+        p1 = np.zeros(m, dtype=np.complex128); p1[0] = x     # T_1 = x + c h
+        if m > 1:
+            p1[1] = c
+        cur = p0 if self.j == 0 else p1
+        for _ in range(self.j - 1):
+            nxt = 2.0 * x * p1 - p0
+            nxt[1:] += 2.0 * c * p1[:-1]
+            p0, p1 = p1, nxt
+            cur = p1
+        out = np.zeros(k, dtype=np.complex128)
+        out[:min(k, m)] = cur[:k]
+        return out
+
+    def derivs(self, lam, k, scale=1.0):
+        out = self.taylor(lam, k, scale)
+        f = 1.0
+        for i in range(2, min(k, self.j + 1)):               # i! <= j!: no overflow below degree 170
+            f *= i
+            out[i] *= f
+        return out
+
+    def matfun(self, S):
+        S = np.asarray(S)
+        S = S.astype(np.complex128 if np.iscomplexobj(S) else np.float64)
+        I = np.eye(S.shape[0], dtype=S.dtype)
+        X = (2.0 / (self.b - self.a)) * (S - self.a * I) - I
+        T0, T1 = I, X
+        if self.j == 0:
+            return T0
+        for _ in range(self.j - 1):
+            T0, T1 = T1, 2.0 * (X @ T1) - T0
+        return T1
+
+
 class FromMatrixFunction(ScalarFun):
     """Generic fallback for user functions given the reference way: a callable valid for scalars
     and square matrices.  Derivatives via the Jordan-matrix trick of src/NEPTypes.jl:376-388

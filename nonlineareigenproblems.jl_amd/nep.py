@@ -754,6 +754,171 @@ class PEP(AbstractSPMF):
         return [funcs.Monomial(i) for i in range(len(self.A))]
 
 
+# ---- interpolation of a NEP: ChebPEP (src/types_cheb_pep.jl) and interpolate (src/types_poly.jl:101-167) -----------------------
+INTERP_MAX = 64                      # nep_interp_coeffs: 1 <= J, K <= 64
+
+
+def chebyshev_nodes(a, b, k):
+    """the k Chebyshev nodes of [a, b] (types_cheb_pep.jl:6-9), in decreasing order"""
+    a, b, k = float(a), float(b), int(k)
+    return (a + b) / 2 + (b - a) * np.cos((2 * np.arange(1, k + 1) - 1) * np.pi / (2 * k)) / 2
+
+
+def chebyshev_weights(a, b, k):
+    """the k x k table of types_cheb_pep.jl:94-103: row i holds T_i(x_j) 2 / k over the nodes x_j, the first row halved (the
+    primed sum); coefficient i of a function sampled at the nodes is row i times the samples"""
+    x = chebyshev_nodes(a, b, k)
+    T = np.array([funcs.Chebyshev(i, a, b).values(x).real for i in range(int(k))]) * (2.0 / int(k))
+    T[0] *= 0.5
+    return T
+
+
+def interp_coeffs(F, W, C=None, pos=None, beta=0):
+    """C[r(e), :] = beta C[r(e), :] + W F[e, :] on the device (nep_interp_coeffs): F a contiguous (E, J) device tensor, complex128
+    or float64; W a K x J host table; pos an optional int32 device tensor of E distinct rows of C; C a contiguous (rows, K)
+    complex128 device tensor, allocated ((E, K), uninitialised) when it is not given"""
+    W = np.atleast_2d(np.asarray(W))
+    K, J = W.shape
+    if not (F.is_cuda and F.dim() == 2 and F.shape[1] == J and F.is_contiguous() and F.dtype in (CDT, torch.float64)):
+        raise ValueError("interp_coeffs: F must be a contiguous (E, %d) device tensor of complex128 or float64" % J)
+    E = F.shape[0]
+    if C is None:
+        if beta or pos is not None:
+            raise ValueError("interp_coeffs: accumulating or scattering needs the block C")
+        C = torch.empty((E, K), dtype=CDT, device="cuda")
+    if not (C.is_cuda and C.dim() == 2 and C.shape[1] == K and C.is_contiguous() and C.dtype == CDT):
+        raise ValueError("interp_coeffs: C must be a contiguous (rows, %d) complex128 device tensor" % K)
+    if pos is None and C.shape[0] < E:
+        raise ValueError("interp_coeffs: C has fewer rows than F")
+    if pos is not None and not (pos.is_cuda and pos.dtype == torch.int32 and pos.is_contiguous() and pos.numel() == E):
+        raise ValueError("interp_coeffs: pos must be a contiguous int32 device tensor with one row number per entry")
+    Wf = _lib.as_c128(W, "F")
+    check(lib.nep_interp_coeffs(E, J, K, c_vp(F.data_ptr()), J, 1 if F.dtype == CDT else 0, hptr(Wf),
+                                c_vp(pos.data_ptr()) if pos is not None else None, int(beta), c_vp(C.data_ptr()), K, stream_ptr()))
+    return C
+
+
+def _csc_keys(M, n):
+    """entry keys column * n + row of a CSC matrix with sorted indices (the keys of _aligned_terms)"""
+    return np.repeat(np.arange(M.shape[1], dtype=np.int64), np.diff(M.indptr)) * n + M.indices
+
+
+def _interp_table_route_ok(orgnep):
+    """a pure SPMF (no terms outside its matrices: the purity test of lu_from_terms) with sparse matrices, at most 64 of them"""
+    return (isinstance(orgnep, AbstractSPMF) and type(orgnep).compute_Mder is AbstractSPMF.compute_Mder
+            and type(orgnep).compute_Mlincomb is AbstractSPMF.compute_Mlincomb and orgnep.issparse()
+            and len(orgnep.get_fv()) <= INTERP_MAX and orgnep._aligned_terms() is not None)
+
+
+def _interp_on_device(orgnep, points, W, table=True):
+    """coefficient matrices sum_j W[i, j] M(points[j]), i < K, computed entry by entry on the device.  Returns (Av, aligned,
+    aligned_dev, real): the K host matrices, and for sparse samples the union pattern with the E x K coefficient block on the
+    host (the `_aligned` of an AbstractSPMF) and on the device with its Gram matrix (`_aligned_dev`); None, None for dense ones.
+
+    table route (a pure sparse SPMF with at most 64 terms whose aligned term block exists): M(x_j) = sum_t f_t(x_j) A_t, so the
+    coefficients are (W [f_t(x_j)]) applied to the term block D that is already on the device; no matrix is assembled.
+    sampling route (anything else): compute_Mder at every point on the host, one upload and one call per sample."""
+    _lib.require_gpu()
+    W = np.atleast_2d(np.asarray(W))
+    K = W.shape[0]
+    points = np.asarray(points)
+    n = orgnep.size(1)
+    if table and _interp_table_route_ok(orgnep):
+        indptr, indices, Dd, _ = orgnep.aligned_terms_dev()
+        Fx = np.column_stack([f.values(points) for f in orgnep.get_fv()])                  # J x m_t
+        Cd = interp_coeffs(Dd, W @ Fx)
+        real = bool(orgnep.is_real() and not np.iscomplexobj(points) and not np.iscomplexobj(W))
+        sparse = True
+    else:
+        samples = [orgnep.compute_Mder(x) for x in points]
+        sparse = all(sp.issparse(S) for S in samples)
+        real = not np.iscomplexobj(W) and all(not np.iscomplexobj(S.data if sp.issparse(S) else S) for S in samples)
+        vdt = lambda v: np.ascontiguousarray(v, dtype=np.complex128 if np.iscomplexobj(v) else np.float64)
+        if sparse:
+            cs = [sp.csc_matrix(S) for S in samples]
+            for M in cs:
+                M.sum_duplicates(); M.sort_indices()
+            keys = [_csc_keys(M, n) for M in cs]           # union from the entry keys: explicitly stored zeros keep their slot
+            keyU = np.unique(np.concatenate(keys))
+            E = len(keyU)
+            indices = (keyU % n).astype(np.int32)
+            indptr = np.concatenate(([0], np.cumsum(np.bincount(keyU // n, minlength=n)))).astype(np.int32)
+            # a first sample on a proper subset of the pattern leaves the other rows to the later samples: they start from zero
+            Cd = (torch.empty if len(keys[0]) == E else torch.zeros)((E, K), dtype=CDT, device="cuda")
+            for j, (M, key) in enumerate(zip(cs, keys)):
+                pos = None
+                if len(key) < E:                           # (a subset of equal size is the pattern itself)
+                    pos = torch.from_numpy(np.searchsorted(keyU, key).astype(np.int32)).to("cuda")
+                if len(key):
+                    interp_coeffs(torch.from_numpy(vdt(M.data)).to("cuda").reshape(-1, 1), W[:, j:j + 1], Cd, pos, beta=int(j > 0))
+        else:
+            E = n * n
+            Cd = torch.empty((E, K), dtype=CDT, device="cuda")
+            for j, S in enumerate(samples):
+                Sd = np.asarray(S.toarray() if sp.issparse(S) else S)
+                interp_coeffs(torch.from_numpy(vdt(Sd).reshape(-1)).to("cuda").reshape(-1, 1), W[:, j:j + 1], Cd, None, beta=int(j > 0))
+    D = Cd.cpu().numpy()                                   # E x K, the one download
+    if not sparse:
+        Av = [(D[:, i].real if real else D[:, i]).reshape(n, n).copy() for i in range(K)]
+        return Av, None, None, real
+    Av = [sp.csc_matrix(((D[:, i].real if real else D[:, i]).copy(), indices, indptr), shape=(n, n)) for i in range(K)]
+    return Av, (indptr, indices, D), (Cd, D.conj().T @ D), real
+
+
+class ChebPEP(SPMF_NEP):
+    """ChebPEP(orgnep, k, a=-1, b=1): M(lam) ~ B_0 T_0(lam) + ... + B_{k-1} T_{k-1}(lam), the interpolant of any NEP in the k
+    Chebyshev nodes of [a, b], stored in the Chebyshev basis scaled to [a, b] (src/types_cheb_pep.jl:122-218).  A plain SPMF for
+    every driver: the functions are funcs.Chebyshev with closed-form derivatives and matrix functions, the coefficient matrices are
+    host matrices (sparse when the samples are, real when the source is) formed on the device by nep_interp_coeffs.  The block of
+    coefficients on the union pattern is kept as the aligned term block of the new NEP, on the host and on the device, so
+    compute_Mder, compute_Mder_batch and the device LU assembly never build a union pattern again.
+
+    `cosine_formula_cutoff` is accepted for the reference's signature and ignored: there it picks, per degree, between explicit
+    monomial expressions and cos(j acos x); here every degree is evaluated by the three-term recurrence, which is exact for
+    polynomials in any argument, so there is nothing to switch between."""
+
+    def __init__(self, orgnep, k, a=-1, b=1, cosine_formula_cutoff=5):
+        k = int(k)
+        if k < 1:
+            raise ValueError("ChebPEP: at least one interpolation node is needed (k = %d)" % k)
+        if k > INTERP_MAX:
+            raise ValueError("ChebPEP: at most %d interpolation nodes are supported (k = %d)" % (INTERP_MAX, k))
+        fv = [funcs.Chebyshev(i, a, b) for i in range(k)]            # (raises for a >= b)
+        self.a, self.b, self.k = fv[0].a, fv[0].b, k
+        self.n = orgnep.size(1)
+        Av, aligned, aligned_dev, _ = _interp_on_device(orgnep, chebyshev_nodes(self.a, self.b, k), chebyshev_weights(self.a, self.b, k))
+        self.A, self.fi = Av, fv
+        self._aligned = aligned
+        if aligned_dev is not None:
+            self._aligned_dev = aligned_dev
+
+
+def interpolate(nep, intpoints, T=complex):
+    """the PEP (monomial basis) of degree len(intpoints) - 1 that equals `nep` at the points `intpoints` (src/types_poly.jl:101-167);
+    T: element type of its matrices (complex or float).  The inverse of the Vandermonde matrix is formed once on the host (an LU
+    solve against the identity) and applied entry by entry on the device (nep_interp_coeffs), one call per sample."""
+    import scipy.linalg as sla
+    x = np.asarray(intpoints).reshape(-1)
+    d = len(x)
+    if d < 1 or d > INTERP_MAX:
+        raise ValueError("interpolate: 1 to %d interpolation points are supported (%d given)" % (INTERP_MAX, d))
+    want_real = np.dtype(T).kind == "f"
+    if want_real and np.iscomplexobj(x):
+        raise ValueError("interpolate: real matrices need real interpolation points")
+    V = np.vander(x.astype(np.float64 if want_real or not np.iscomplexobj(x) else np.complex128), d, increasing=True)
+    W = sla.lu_solve(sla.lu_factor(V), np.eye(d))
+    Av, aligned, aligned_dev, real = _interp_on_device(nep, x, W, table=False)
+    if want_real and not real:
+        raise ValueError("interpolate: the problem is complex at the interpolation points, T = float cannot hold it")
+    if not want_real:
+        Av = [A.astype(np.complex128) for A in Av]
+    pep = PEP(Av)
+    pep._aligned = aligned
+    if aligned_dev is not None:
+        pep._aligned_dev = aligned_dev
+    return pep
+
+
 class SumNEP(AbstractSPMF):
     """SPMFSumNEP (src/NEPTypes.jl:845-898): the stacked CSR simply holds the terms of both halves."""
 

@@ -16,7 +16,7 @@ import torch
 
 from . import dense
 from .exceptions import NoConvergenceException
-from .nep import AbstractSPMF, CDT, DEP, PEP, SPMF_NEP, is_dev, to_dev
+from .nep import AbstractSPMF, CDT, ChebPEP, DEP, PEP, SPMF_NEP, is_dev, to_dev
 
 EPS = np.finfo(float).eps
 
@@ -172,10 +172,116 @@ class PolyeigInnerSolver(InnerSolver):
     """src/inner_solver.jl:104,298-304: companion linearisation of the projected PEP (host LAPACK, k*d x k*d)"""
 
 
-def polyeig(Bv):
-    """eigenpairs of sum_i lam^i B_i through the first companion form (src/method_companion.jl); returns (lam, V) with
-    the leading-block eigenvectors normalised"""
+def companion(pep):
+    """(E, A) with A x = lam E x the companion linearisation of a PEP of degree d, both d n x d n (src/method_companion.jl:30-60):
+    E = diag(A_d, I, ..., I), A = -[[A_{d-1} ... A_0], [-I 0]]; sparse when the PEP is"""
+    import scipy.sparse as sp
+    Av = pep.get_Av()
+    d, n = len(Av) - 1, pep.size(1)
+    if d < 1:
+        raise ValueError("companion: the PEP needs degree at least 1")
+    if pep.issparse():
+        I = sp.identity(n * (d - 1), format="csc")
+        E = sp.block_diag([sp.csc_matrix(Av[d]), I], format="csc") if d > 1 else sp.csc_matrix(Av[d])
+        top = sp.hstack([-sp.csc_matrix(Av[d - 1 - i]) for i in range(d)], format="csc")
+        A = sp.vstack([top, sp.hstack([I, sp.csc_matrix((n * (d - 1), n))], format="csc")], format="csc") if d > 1 else top
+        return E, A
+    dt = np.result_type(*[np.asarray(M).dtype for M in Av])
+    E = np.eye(n * d, dtype=dt); A = np.zeros((n * d, n * d), dtype=dt)
+    E[:n, :n] = np.asarray(Av[d])
+    for i in range(d):
+        A[:n, i * n:(i + 1) * n] = -np.asarray(Av[d - 1 - i])
+    A[n:, :n * (d - 1)] = np.eye(n * (d - 1), dtype=dt)
+    return E, A
+
+
+def colleague_pencil(Bv, sparse=False):
+    """(L0, L1) with L0 z = theta L1 z the linearisation of sum_i T_i(theta) B_i, T_i the Chebyshev polynomials on [-1, 1] and
+    z = [T_0(theta) v; ...; T_{k-2}(theta) v], both n (k - 1) x n (k - 1) (src/method_companion.jl:134-162; Amiraslani, Corless
+    and Lancaster 2009; Effenberger and Kressner 2012): the recurrence T_{j-1} + T_{j+1} = 2 theta T_j in the first k - 2 block
+    rows, the polynomial itself with T_{k-1} eliminated in the last one.  Needs k >= 3 coefficients (the last block row reaches back
+    to block k - 3).  sparse: scipy CSC matrices (the B_i may be sparse or dense), otherwise dense arrays."""
+    import scipy.sparse as sp
+    k = len(Bv)
+    if k < 3:
+        raise ValueError("colleague_pencil: at least 3 Chebyshev coefficients are needed (k = %d)" % k)
+    n = Bv[0].shape[0]
+    if sparse:
+        Bs = [sp.csc_matrix(B) for B in Bv]
+        I = sp.identity(n, format="csc")
+        L0 = [[None] * (k - 1) for _ in range(k - 1)]
+        L1 = [[None] * (k - 1) for _ in range(k - 1)]
+        for j in range(k - 2):
+            L0[j][j + 1] = I
+            if j + 1 < k - 2:
+                L0[j + 1][j] = I
+            L1[j][j] = I if j == 0 else 2 * I
+        for c in range(k - 1):
+            L0[k - 2][c] = -Bs[c]
+        L0[k - 2][k - 3] = L0[k - 2][k - 3] + Bs[k - 1]
+        L1[k - 2][k - 2] = 2 * Bs[k - 1]
+        return sp.bmat(L0, format="csc"), sp.bmat(L1, format="csc")
+    Bd = [np.asarray(B.toarray() if sp.issparse(B) else B) for B in Bv]
+    dt = np.result_type(*[B.dtype for B in Bd], np.float64)
+    N = n * (k - 1)
+    L0 = np.zeros((N, N), dtype=dt); L1 = np.zeros((N, N), dtype=dt)
+    I = np.eye(n, dtype=dt)
+    blk = lambda M, r, c: M[r * n:(r + 1) * n, c * n:(c + 1) * n]
+    for j in range(k - 2):
+        blk(L0, j, j + 1)[:] = I
+        blk(L0, j + 1, j)[:] = I
+        blk(L1, j, j)[:] = I if j == 0 else 2 * I
+    for c in range(k - 1):
+        blk(L0, k - 2, c)[:] = -Bd[c]
+    blk(L0, k - 2, k - 3)[:] += Bd[k - 1]
+    blk(L1, k - 2, k - 2)[:] = 2 * Bd[k - 1]
+    return L0, L1
+
+
+def _leading_blocks(X, n):
+    X = np.asarray(X)[:n, :]
+    nrm = np.linalg.norm(X, axis=0)
+    return X / np.where(nrm > 0, nrm, 1.0)[None, :]
+
+
+def _polyeig_nep(nep, eigsolvertype, nev, target):
+    """polyeig of a PEP (companion form) or a ChebPEP (colleague pencil in theta = 2 (lam - a) / (b - a) - 1)"""
     import scipy.linalg as sla
+    n = nep.size(1)
+    if isinstance(nep, ChebPEP):
+        if nep.k < 3:
+            raise ValueError("polyeig: a ChebPEP needs at least 3 coefficients (k = %d)" % nep.k)
+        a, b = nep.a, nep.b
+        back = lambda th: (b - a) * (np.asarray(th) + 1) / 2 + a
+        if eigsolvertype is None:                                     # the reference: dense LAPACK, all n (k - 1) values
+            L0, L1 = colleague_pencil(nep.get_Av())
+            th, X = sla.eig(L0, L1)
+            return back(th), _leading_blocks(X, n)
+        L0, L1 = colleague_pencil(nep.get_Av(), sparse=True)
+        N = L0.shape[0]
+        th, X = eigsolvertype(L0, L1).eig_solve(nev=N if nev is None else int(nev),
+                                                target=2 * (complex(0 if target is None else target) - a) / (b - a) - 1)
+        return back(th), _leading_blocks(X, n)
+    if eigsolvertype is None:
+        return polyeig(nep.get_Av())
+    E, A = companion(nep)
+    lam, X = eigsolvertype(A, E).eig_solve(nev=A.shape[0] if nev is None else int(nev), target=1 if target is None else target)
+    return np.asarray(lam, dtype=complex), _leading_blocks(X, n)
+
+
+def polyeig(Bv, eigsolvertype=None, nev=None, target=None):
+    """eigenpairs of sum_i lam^i B_i through the first companion form (src/method_companion.jl); returns (lam, V) with
+    the leading-block eigenvectors normalised.  Bv: a list of matrices, a PEP (its get_Av()), or a ChebPEP (the colleague pencil
+    of its Chebyshev coefficients, eigenvalues mapped back to [a, b]'s variable; needs k >= 3).  The default is dense LAPACK on
+    the host with all eigenvalues; eigsolvertype (an EigSolver class, e.g. ArnoldiEigSolver) with nev and target solves the
+    sparse pencil instead: for a ChebPEP the device Krylov-Schur solver on (L0, L1) with the target mapped to theta."""
+    import scipy.linalg as sla
+    if hasattr(Bv, "get_Av"):
+        if not isinstance(Bv, (PEP, ChebPEP)):
+            raise TypeError("polyeig takes a list of matrices, a PEP or a ChebPEP")
+        return _polyeig_nep(Bv, eigsolvertype, nev, target)
+    if eigsolvertype is not None or nev is not None or target is not None:
+        raise TypeError("polyeig: eigsolvertype, nev and target apply to a PEP or a ChebPEP")
     d = len(Bv) - 1
     k = Bv[0].shape[0]
     if d == 1:
