@@ -189,6 +189,19 @@ int32_t nep_lr_hankel(nep_spmf* s, int32_t ma, int32_t mb, const nep_cdouble* dW
                       int64_t ldb, const nep_cdouble* dTau, int64_t ldt, nep_cdouble* h_c, nep_cdouble* d_c,
                       nep_stream stream);
 
+/* K14  out[i + kw*(j + kv*t)] = w_i^H A_t v_j for every term t < mt: the unsummed bilinear forms of the SPMF.
+ * replaces: the `dot(y, nep.A[i]*x)` loop of compute_rf src/compute_rf_wrapper.jl:115-118, the two compute_Mlincomb calls and
+ *           dots per scalar Newton step of :31-39 (y^H M(lam) x = sum_t f_t(lam) y^H A_t x needs the forms once), and the
+ *           per-term W' * (A_t * V) of set_projectmatrices! src/NEPTypes.jl:724-741.
+ * dW: n x kw (ldw), dV: n x kv (ldv), column-major device blocks; dW == dV is allowed; rows >= n of a column are never read.
+ * The stacked CSR is read once for all terms when mt*kv <= 32 (ceil(kv / floor(32 / mt)) times beyond; kw = kv = 1 is one pass
+ * for every mt), two launches, no intermediate of size n x kv, no atomics, fixed summation order: two calls give the same bits.
+ * h_out != NULL: the mt*kw*kv results to the host (synchronous); otherwise to the device block d_out (asynchronous).
+ * NEP_ERR_UNSUPPORTED (nothing launched) unless 1 <= kw, kv <= 32 and mt*kw*kv <= 3072; NEP_ERR_ARG (nothing launched) for a
+ * NULL handle or block, ldw < n, ldv < n, or both outputs NULL. */
+int32_t nep_spmf_biforms(nep_spmf* s, int32_t kw, const nep_cdouble* dW, int64_t ldw, int32_t kv, const nep_cdouble* dV,
+                         int64_t ldv, nep_cdouble* h_out, nep_cdouble* d_out, nep_stream stream);
+
 /* Expansion step of compute_Mlincomb on a deflated NEP (Effenberger deflation).  With X = V0 (n0 x p), V = [V1; V2]
  * (k columns of n0 + p rows), s = startder, K = k + s, e_i = i + s:
  *   Vn[:, j] = [j >= s] a_{j-s} V1[:, j-s] + X sum_{i : e_i >= j} G[i, j] W_{e_i - j} V2[:, i],   j = 0..K-1

@@ -507,6 +507,14 @@ gemv_hd!(y::DevBuf, A::DevBuf, x::DevBuf, d::Union{DevBuf,Nothing}) =
 interp_coeffs!(C::DevBuf, W::Matrix{ComplexF64}, F::DevBuf, β::Integer = 0) =
     chk(ccall((:nep_interp_coeffs, LIB), Cint, (Int64, Int32, Int32, Ptr{Cvoid}, Int64, Int32, Ptr{ComplexF64}, Ptr{Cvoid}, Int32,
               Ptr{Cvoid}, Int64, Ptr{Cvoid}), F.cols, F.rows, C.rows, F.ptr, F.rows, 1, W, C_NULL, β, C.ptr, C.rows, C_NULL))
+# K14: F[i, j, t] = W[:, i]' * A_t * V[:, j] for every term of the SPMF in one pass over the stacked CSR: the loop of
+# dot(y, nep.A[i]*x) in compute_rf (compute_rf_wrapper.jl:115-118), the forms behind y' M(λ) x = Σ_t f_t(λ) (y' A_t x), and the
+# matrices W' A_t V of a projected NEP (src/NEPTypes.jl:724-741)
+function biforms(d::DeviceSPMF, W::DevBuf, V::DevBuf)
+    F = Array{ComplexF64,3}(undef, W.cols, V.cols, length(get_Av(d)))
+    chk(ccall((:nep_spmf_biforms, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Int64, Ptr{ComplexF64},
+              Ptr{Cvoid}, Ptr{Cvoid}), d.handle, W.cols, W.ptr, W.rows, V.cols, V.ptr, V.rows, F, C_NULL, C_NULL)); F
+end
 
 # ---- quadrature seam (src/method_contour_common.jl:46,61-94): nodes sharded over ranks, RCCL all-gather ------
 # One Julia process per GPU (e.g. `mpiexec -n 8 julia ...` with MPI.jl only as the launcher / unique-id carrier).

@@ -30,7 +30,9 @@ from .infbilanczos import infbilanczos, left_right_scalar_prod
 from .deflation import (deflate_eigpair, get_deflated_eigpairs, normalize_schur_pair, verify_deflate_mode, DeflatedNEPMM,
                         DeflatedGenericNEP, DeflatedSPMF)
 from .projection import (Proj_SPMF_NEP, create_proj_NEP, inner_solve, InnerSolver, DefaultInnerSolver, IARInnerSolver,
-                         NewtonInnerSolver, IARChebInnerSolver, PolyeigInnerSolver, polyeig, companion, colleague_pencil)
+                         NewtonInnerSolver, IARChebInnerSolver, PolyeigInnerSolver, SGIterInnerSolver, polyeig, companion,
+                         colleague_pencil)
+from .sgiter import sgiter, choose_correct_eigenvalue_from_rf, gershgorin_shift
 from .nleigs import nleigs, NleigsSolutionDetails
 from .aaaeigs import AAAeigs, svAAA, AAASolutionDetails
 from .broyden import broyden, broyden_T

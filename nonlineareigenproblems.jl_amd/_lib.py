@@ -101,6 +101,7 @@ SIGNATURES = {
     "nep_mlincomb": [c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp],
     "nep_mlincomb_dev": [c_vp, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp],
     "nep_lr_hankel": [c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp],
+    "nep_spmf_biforms": [c_vp, c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp],
     "nep_defl_expand": [c_i64, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp],
     "nep_defl_border": [c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp],
     "nep_cork_expand": [c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, cdouble, c_vp, c_i64, c_vp],

@@ -92,6 +92,26 @@ class ArnoldiEigSolver(EigSolver):
         self.info = {}
         return self
 
+    @classmethod
+    def from_terms(cls, spmf, cA, cB):
+        """the pencil (sum_t cA_t A_t, sum_t cB_t A_t) on the device handle of the pure sparse SPMF `spmf`, the two coefficient
+        rows given directly (sgiter: the terms [A_1..A_m, I] with cA = [f_t(lam).., 0], cB = [0.., 1]).  The rows may be replaced
+        between calls of eig_solve_dev; neither matrix is assembled"""
+        if not cls.accepts(spmf):
+            raise TypeError("ArnoldiEigSolver.from_terms needs a pure sparse SPMF NEP")
+        cA = np.array(cA, dtype=np.complex128).reshape(-1)
+        cB = np.array(cB, dtype=np.complex128).reshape(-1)
+        if len(cA) != len(spmf.get_fv()) or len(cB) != len(cA):
+            raise ValueError("ArnoldiEigSolver.from_terms: one coefficient per term is needed in each row")
+        self = cls.__new__(cls)
+        self.A = self.B = None
+        self._spmf = spmf
+        self.cA, self.cB = cA, cB
+        self._terms_first = True
+        self.n = spmf.n
+        self.info = {}
+        return self
+
     @staticmethod
     def accepts(nep):
         """the purity test of lu_from_terms, and sparse matrices"""

@@ -282,6 +282,33 @@ def beam(n=100):
 GALLERY["beam"] = beam
 
 
+def real_quadratic():
+    """src/gallery_extra/gallery_examples.jl:55-71: a dense 4 x 4 quadratic problem with symmetric matrices and real eigenvalues;
+    the four smallest are 1e3 * (-2.051741417993845, -0.182101627437811, -0.039344930222838, -0.004039879577113)"""
+    A0 = np.array([[4.0, 0, 1, 1], [0, 2, 1, 1], [1, 1, 6, -2], [1, 1, -2, 3]])
+    A1 = np.array([[167.0, -140, 95, -131], [-140, 327, 54, 85], [95, 54, 235, -81], [-131, 85, -81, 181]])
+    A2 = np.array([[2.0, 1, -1, -1], [1, 5, -3, 2], [-1, -3, 3, 0], [-1, 2, 0, 3]])
+    return PEP([A0, A1, A2])
+
+
+GALLERY["real_quadratic"] = real_quadratic
+
+
+def overdamped_qep_sparse(n=257):
+    """a sparse overdamped quadratic problem lam^2 I + lam A1 + A0 with symmetric real matrices (all 2 n eigenvalues real; the
+    n largest lie in [-1.5, 0], where the Rayleigh functional is unique): the min-max family sgiter is tested on at sizes
+    where the eigen step is a sparse one.  With i = 0..n-1: A0 = tridiag(-1, 2, -1) + diag(0.5 + 2 i / n),
+    A1 = diag(9 + 3 sin^2(0.37 i)) with 0.7 cos(i) at (i, i + 2) and (i + 2, i)."""
+    i = np.arange(n, dtype=float)
+    A0 = sp.diags([-np.ones(n - 1), 2.0 + 0.5 + 2.0 * i / n, -np.ones(n - 1)], [-1, 0, 1], format="csc")
+    off = 0.7 * np.cos(i[:max(n - 2, 0)])
+    A1 = sp.diags([off, 9.0 + 3.0 * np.sin(0.37 * i) ** 2, off], [-2, 0, 2], format="csc")
+    return PEP([sp.csc_matrix(A0), sp.csc_matrix(A1), sp.identity(n, format="csc")])
+
+
+GALLERY["overdamped_qep_sparse"] = overdamped_qep_sparse
+
+
 def particle_nep(interval):
     """The "particle in a canyon" problem of test/nleigs/particle_test_utils.jl:37-165 (after W. Vandenberghe): a 2-D
     Schroedinger operator H - lam I on a 201 x 81 grid plus, per branch point (eigenvalue of the lead Hamiltonian), a

@@ -20,7 +20,7 @@ from .exceptions import NoConvergenceException
 from .deflation import deflate_eigpair, get_deflated_eigpairs, verify_deflate_mode
 from .linsolvers import DefaultLinSolverCreator, DeflatedNEPLinSolverCreator, create_linsolver
 from .nep import CDT, to_dev, to_host
-from .projection import DefaultInnerSolver, create_proj_NEP, inner_solve
+from .projection import DefaultInnerSolver, SGIterInnerSolver, create_proj_NEP, inner_solve
 
 EPS = np.finfo(float).eps
 
@@ -40,6 +40,8 @@ def jd_betcke(nep, maxit=100, neigs=1, projtype="PetrovGalerkin", inner_solver_m
         raise ValueError("maxit = %d is larger than size of NEP = %d." % (maxit, n))
     if projtype not in ("Galerkin", "PetrovGalerkin"):
         raise ValueError("Only accepted values of 'projtype' are :Galerkin and :PetrovGalerkin.")
+    if projtype != "Galerkin" and isinstance(inner_solver_method, SGIterInnerSolver):
+        raise ValueError("Need to use 'projtype' :Galerkin in order to use SGITER as inner solver.")
     if inner_solver_method is None:
         inner_solver_method = DefaultInnerSolver()
     if errmeasure is None:
@@ -106,12 +108,14 @@ def jd_effenberger(nep, maxit=100, neigs=1, inner_solver_method=None, orthmethod
     get_deflated_eigpairs of the last deflated NEP: (eigenvalues, n x neigs eigenvectors of `nep`).  Raises
     NoConvergenceException (holding the pairs found so far and the current iterate) when the budget runs out.
 
-    Differences from the reference: the projected NEP of this backend needs an AbstractSPMF, so a `deflation_mode` that does
-    not resolve to "SPMF" is refused up front (the reference fails with a MethodError after the first pair); there is no
-    SGIterInnerSolver here, so the reference's refusal of it has no counterpart."""
+    Difference from the reference: the projected NEP of this backend needs an AbstractSPMF, so a `deflation_mode` that does
+    not resolve to "SPMF" is refused up front (the reference fails with a MethodError after the first pair).  SGIterInnerSolver
+    is refused as there (:239-241): a deflated problem has no min-max characterisation."""
     n = nep.size(1)
     if maxit > n:
         raise ValueError("maxit = %d is larger than size of NEP = %d." % (maxit, n))
+    if isinstance(inner_solver_method, SGIterInnerSolver):
+        raise ValueError("Inner solver 'SGIterInnerSolver' not accepted since deflated problem not min-max.")
     if verify_deflate_mode(nep, deflation_mode) != "SPMF":
         raise ValueError("jd_effenberger projects the deflated NEP, which needs deflation_mode \"SPMF\" (an AbstractSPMF)")
     if inner_solver_method is None:

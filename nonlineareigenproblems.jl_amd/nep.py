@@ -177,6 +177,23 @@ class SPMFDevice:
                                    stream_ptr()))
         return z
 
+    def biforms(self, W, V, out=None):
+        """K14 (nep_spmf_biforms): the forms w_i^H A_t v_j of every term in one pass over the stacked CSR.  W, V: device
+        vectors (n,) or column-major blocks ((k, ld) tensors, ld >= n); W may be V.  Without `out` the result comes back to
+        the host as an array of shape (mt, kv, kw) (entry [t, j, i]; synchronous); with `out` (a complex128 device tensor of
+        mt kv kw words) it stays on the device and the call is asynchronous."""
+        W2 = W if W.dim() == 2 else W.reshape(1, -1)
+        V2 = V if V.dim() == 2 else V.reshape(1, -1)
+        kw, kv = W2.shape[0], V2.shape[0]
+        args = (self.h, kw, dptr(W2), W2.shape[1], kv, dptr(V2), V2.shape[1])
+        if out is not None:
+            assert out.dtype == CDT and out.is_contiguous() and out.numel() >= self.mt * kw * kv
+            check(lib.nep_spmf_biforms(*args, None, c_vp(out.data_ptr()), stream_ptr()))
+            return out
+        h = np.empty((self.mt, kv, kw), dtype=np.complex128)
+        check(lib.nep_spmf_biforms(*args, hptr(h), None, stream_ptr()))
+        return h
+
     def resid_batch(self, F, QT, k, ldq):
         Fm = _lib.as_c128(F, "F")
         assert Fm.shape == (self.mt, k)

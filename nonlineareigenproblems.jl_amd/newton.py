@@ -44,11 +44,92 @@ def _mder_times(nep, lam, vb, out, der):
     return out
 
 
-def compute_rf(nep, x, inner_solver=None, y=None, target=0.0, lam=None):
-    """Rayleigh functional by scalar Newton: y^H M(lam) x = 0  (compute_rf_wrapper.jl:25-54).
-    x, y: device vectors (n,) or NumPy vectors.  Returns a length-1 complex array."""
+def _host_vec(x):
+    return to_host(x.reshape(1, -1))[:, 0] if torch.is_tensor(x) else np.asarray(x, dtype=np.complex128).reshape(-1)
+
+
+def rf_forms_ok(nep):
+    """the bilinear forms determine y^H M(lam) x: an SPMF with nothing outside its matrices (or the projection of one)"""
+    from .nep import AbstractSPMF
+    from .projection import Proj_SPMF_NEP
+    if isinstance(nep, Proj_SPMF_NEP):
+        return nep.nep_proj is not None
+    return isinstance(nep, AbstractSPMF) and type(nep).compute_Mlincomb is AbstractSPMF.compute_Mlincomb
+
+
+def spmf_forms(nep, y, x):
+    """q_t = y^H A_t x for every term of the SPMF `nep`, as a host vector: one pass of K14 (nep_spmf_biforms) over the
+    stacked CSR for sparse matrices (x, y on the device or uploaded), plain NumPy for dense host matrices"""
+    from .projection import Proj_SPMF_NEP
+    if not rf_forms_ok(nep):
+        raise TypeError("the bilinear forms y^H A_t x need an SPMF without terms outside its matrices (type %s)" % type(nep).__name__)
+    if isinstance(nep, Proj_SPMF_NEP):
+        nep = nep.nep_proj
+    if not nep.issparse():
+        xh, yh = _host_vec(x), _host_vec(x if y is None else y)
+        return np.array([np.vdot(yh, np.asarray(A) @ xh) for A in nep.get_Av()], dtype=np.complex128)
+    xd = x if torch.is_tensor(x) else to_dev(x)[0]
+    yd = xd if y is None else (y if torch.is_tensor(y) else to_dev(y)[0])
+    return nep.dev.biforms(yd, xd).reshape(-1)
+
+
+def _rf_polyeig(nep, x, y, target):
+    """compute_rf_wrapper.jl:112-135: the roots of sum_i (y^H A_i x) lam^i, sorted by their distance to the target"""
+    from .nep import PEP
+    if not isinstance(nep, PEP):
+        raise TypeError("Wrong type. PolyeigInnerSolver only handles the PEP type.")
+    a = spmf_forms(nep, y, x)
+    pp = np.roots(a[::-1])                              # the eigenvalues of the companion matrix of :121-128
+    return pp[np.argsort(np.abs(pp - target), kind="stable")]
+
+
+def _rf_inner_solve(nep, x, y, inner_solver, target, lam, tol):
+    """compute_rf_wrapper.jl:82-107: the 1 x 1 projected problem sum_t f_t(lam) (y^H A_t x), handed to inner_solve"""
+    from .projection import Proj_SPMF_NEP, inner_solve
+    if isinstance(nep, Proj_SPMF_NEP):
+        nep = nep.nep_proj
+    q = spmf_forms(nep, y, x)
+    pnep = Proj_SPMF_NEP.__new__(Proj_SPMF_NEP)          # the forms ARE the projected matrices: no device pass of its own
+    pnep.orgnep, pnep.orgnep_Av, pnep.orgnep_fv, pnep.maxsize = nep, nep.get_Av(), nep.get_fv(), 1
+    pnep.projnep_B_mem = [np.array([[qt]], dtype=np.complex128) for qt in q]
+    pnep._rebuild(1)
+    try:
+        lamv, _ = inner_solve(inner_solver, pnep, lamv=[lam], sigma=target, tol=tol)
+    except NoConvergenceException as e:                  # even return the approximation upon failure
+        lamv = e.lam
+    return np.atleast_1d(np.asarray(lamv, dtype=np.complex128))
+
+
+def compute_rf(nep, x, inner_solver=None, y=None, target=0.0, lam=None, forms=False, tol=EPS * 1e3):
+    """Rayleigh functional: the values lam with y^H M(lam) x = 0.  x, y: device vectors (n,) or NumPy vectors.
+
+    ScalarNewtonInnerSolver (the default; compute_rf_wrapper.jl:25-54): scalar Newton, a length-1 complex array.  forms=False
+    evaluates y^H M(lam) x and y^H M'(lam) x with two SpMVs and a dot per step; forms=True (an SPMF without terms outside its
+    matrices) computes q_t = y^H A_t x once (K14) and runs the same iteration on sum_t f_t(lam) q_t on the host.
+    PolyeigInnerSolver (:112-135, a PEP): all roots of sum_i (y^H A_i x) lam^i, sorted by |root - target|.
+    Any other InnerSolver (:82-107): inner_solve on the 1 x 1 projected problem (`tol` is passed on); on
+    NoConvergenceException the exception's approximation is returned."""
+    from .projection import InnerSolver, PolyeigInnerSolver
     if inner_solver is None:
         inner_solver = ScalarNewtonInnerSolver()
+    if isinstance(inner_solver, PolyeigInnerSolver):
+        return _rf_polyeig(nep, x, y, target)
+    if isinstance(inner_solver, InnerSolver):
+        return _rf_inner_solve(nep, x, y, inner_solver, target, target if lam is None else lam, tol)
+    if forms:
+        from .projection import Proj_SPMF_NEP
+        q = spmf_forms(nep, y, x)
+        fv = (nep.nep_proj if isinstance(nep, Proj_SPMF_NEP) else nep).get_fv()
+        lam_iter = complex(target if lam is None else lam)
+        dlam = np.inf; count = 0
+        while abs(dlam) > inner_solver.tol and count < inner_solver.maxit:
+            count += 1
+            d = np.array([f.derivs(lam_iter, 2)[:2] for f in fv], dtype=np.complex128)
+            dlam = -(q @ d[:, 0]) / (q @ d[:, 1])
+            lam_iter += dlam
+        if count == inner_solver.maxit and not inner_solver.bad_solution_allowed:
+            raise NoConvergenceException(lam_iter, None, None, "compute_rf: scalar Newton did not converge")
+        return np.array([lam_iter])
     n = nep.size(1)
     xd = x if torch.is_tensor(x) else to_dev(x)[0]
     yd = xd if y is None else (y if torch.is_tensor(y) else to_dev(y)[0])

@@ -172,6 +172,11 @@ class PolyeigInnerSolver(InnerSolver):
     """src/inner_solver.jl:104,298-304: companion linearisation of the projected PEP (host LAPACK, k*d x k*d)"""
 
 
+class SGIterInnerSolver(InnerSolver):
+    """src/inner_solver.jl:172-178,350-354: safeguarded iteration on the projected (Hermitian) problem; `j`, the number of the
+    wanted eigenvalue, is the caller's keyword j, by default neigs (jd_betcke passes the number of converged pairs plus one)"""
+
+
 def companion(pep):
     """(E, A) with A x = lam E x the companion linearisation of a PEP of degree d, both d n x d n (src/method_companion.jl:30-60):
     E = diag(A_d, I, ..., I), A = -[[A_{d-1} ... A_0], [-I 0]]; sparse when the PEP is"""
@@ -316,6 +321,10 @@ def inner_solve(solver, pnep, lamv=None, V=None, neigs=10, sigma=0.0, tol=None, 
         if not isinstance(pnep.orgnep, PEP):
             raise TypeError("Wrong type. PolyeigInnerSolver only handles the PEP type.")
         return polyeig(pnep.get_Av())
+    if isinstance(solver, SGIterInnerSolver):
+        from .sgiter import sgiter as _sgiter
+        lam, v = _sgiter(pnep, int(kwargs.get("j", neigs)))
+        return np.array([lam]), np.asarray(v).reshape(k, 1)
     if isinstance(solver, IARInnerSolver):
         nep = pnep.nep_proj
         if isinstance(pnep.orgnep, DEP) and solver.normalize_DEPs:          # :312-324
