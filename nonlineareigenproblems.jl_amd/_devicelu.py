@@ -14,7 +14,7 @@ from . import _lib
 from ._env import env_float, env_int, env_str
 from ._hostlu_pool import _nep_hostlu
 from ._lib import lib, check, hptr, c_vp, c_i64
-from .nep import stream_ptr
+from .nep import pure_spmf, stream_ptr
 
 
 def host_factor(Ac, permc_spec=None, diag_pivot_thresh=None, symmetric_mode=None):
@@ -210,6 +210,7 @@ class _DeviceRefactor:
             cls.plans.clear()
 
 
+GROWTH_UNREFINED = _DeviceRefactor.GROWTH_UNREFINED      # (read once per process, with the class: the name other modules use)
 atexit.register(_DeviceRefactor.wait)      # a plan thread inside the HIP runtime must not be cut off by interpreter shutdown
 
 
@@ -391,33 +392,69 @@ class DeviceLU:
         return out
 
 
-def lu_from_terms(nep, lam, permc_spec, lu_kw):
-    """M(lam) = sum_t f_t(lam) A_t of a pure SPMF NEP whose pattern has a device-factorisation plan: the m_t coefficients go
-    to the device, the values are assembled there (k_lu_init_terms) and factorised with the stored pivot sequence -- no
-    compute_Mder on the host, no value upload, no pattern hash (1 ms of the 4.4 ms a gun linear solver took).  None: the
-    caller takes the general route (no plan yet, other options, a refusal)."""
-    if (permc_spec is not None or set(lu_kw) - {"expected_solves"} or not _DeviceRefactor.enabled()
-            or env_str("NEP_LU_TERMS", "1") == "0"):
+class TermsRoute:
+    """where a pure SPMF NEP's matrices sum_t c_t A_t are factorised on the device: the union `pattern` of its terms, that pattern's
+    ready `plan` (None: not planned yet, or switched off), the nnz x m_t term values `D_dev` on the device and their Gram matrix `G`"""
+
+    def __init__(self, n, pattern, plan, D_dev, G):
+        self.n, self.pattern, self.plan, self.D_dev, self.G = n, pattern, plan, D_dev, G
+
+
+def terms_route(nep):
+    """the TermsRoute of `nep`, or None: device factorisation switched off, a NEP with parts outside its SPMF terms (a plan keyed by
+    the terms' pattern would factorise the terms alone), a dense term.  Nothing is uploaded for a NEP that is refused."""
+    if not _DeviceRefactor.enabled():
         return None
-    from .nep import AbstractSPMF
-    if not (isinstance(nep, AbstractSPMF) and type(nep).compute_Mder is AbstractSPMF.compute_Mder
-            and hasattr(nep, "aligned_terms_dev")):
-        return None
-    if not _DeviceRefactor.plans:                      # nothing planned yet: do not build the device term block for it
+    if not (pure_spmf(nep, "Mder") and hasattr(nep, "aligned_terms_dev")):
         return None
     al = nep.aligned_terms_dev()
     if al is None:
         return None
     indptr, indices, D_dev, G = al
-    plan = _DeviceRefactor.lookup(_DeviceRefactor.key(_Pattern(indptr, indices, (nep.n, nep.n)), (None, None, None)))
-    if plan is None:
+    pattern = _Pattern(indptr, indices, (nep.n, nep.n))
+    return TermsRoute(nep.n, pattern, _DeviceRefactor.lookup(_DeviceRefactor.key(pattern, (None, None, None))), D_dev, G)
+
+
+def factor_term_rows(route, Cf, expected_solves, growth=None):
+    """the matrices sum_t Cf[b, t] A_t (Cf: B x m_t) factorised in one batch with the stored pivot sequence of the route's plan:
+    only the coefficients travel, the values are formed on the device (k_lu_init_terms) and ||.||_F comes from the Gram matrix.
+    growth: the element growth accepted (None: _DeviceRefactor.GROWTH; GROWTH_UNREFINED for factors whose solves no refinement
+    follows).  A list of DeviceLU with None where that matrix was refused; None without a ready plan."""
+    if route is None or route.plan is None:
         return None
-    Cf = np.array([[f.derivs(lam, 1)[0] for f in nep.get_fv()]], dtype=np.complex128)
-    normA = np.sqrt(np.maximum(np.einsum("bs,st,bt->b", Cf.conj(), G, Cf).real, 0.0))
-    lu = _DeviceRefactor.factor_batch_terms(plan, nep.n, D_dev, Cf, normA, expected_solves=int(reused(lu_kw)["expected_solves"]))[0]
+    Cf = np.asarray(Cf, dtype=np.complex128)
+    normA = np.sqrt(np.maximum(np.einsum("bs,st,bt->b", Cf.conj(), route.G, Cf).real, 0.0))
+    return _DeviceRefactor.factor_batch_terms(route.plan, route.n, route.D_dev, Cf, normA, expected_solves=expected_solves,
+                                              growth=growth)
+
+
+def _single_terms_route(nep, lu_kw):
+    """the route of lu_from_terms and lu_from_term_coeffs (one matrix, a factorisation that is reused), or None"""
+    if set(lu_kw) - {"expected_solves"} or env_str("NEP_LU_TERMS", "1") == "0":
+        return None
+    if not _DeviceRefactor.plans:                      # nothing planned yet: do not build the device term block for it
+        return None
+    route = terms_route(nep)
+    return route if (route is not None and route.plan is not None) else None
+
+
+def _single_from_row(route, Cf, lu_kw):
+    """the one matrix sum_t Cf[0, t] A_t factorised on the route's plan for reuse, with the strategy note of a single factorisation"""
+    lu = factor_term_rows(route, Cf, int(reused(lu_kw)["expected_solves"]))[0]
     if lu is not None:
-        lu.strategy = dict(plan["strategy"], numeric="device (stored pivot sequence)")
+        lu.strategy = dict(route.plan["strategy"], numeric="device (stored pivot sequence)")
     return lu
+
+
+def lu_from_terms(nep, lam, permc_spec, lu_kw):
+    """M(lam) = sum_t f_t(lam) A_t of a pure SPMF NEP whose pattern has a device-factorisation plan: the m_t coefficients go
+    to the device, the values are assembled there (k_lu_init_terms) and factorised with the stored pivot sequence -- no
+    compute_Mder on the host, no value upload, no pattern hash (1 ms of the 4.4 ms a gun linear solver took).  None: the
+    caller takes the general route (no plan yet, other options, a refusal)."""
+    route = _single_terms_route(nep, lu_kw) if permc_spec is None else None
+    if route is None:
+        return None
+    return _single_from_row(route, [[f.derivs(lam, 1)[0] for f in nep.get_fv()]], lu_kw)
 
 
 def lu_from_term_coeffs(nep, coef, lu_kw=None):
@@ -426,27 +463,10 @@ def lu_from_term_coeffs(nep, coef, lu_kw=None):
     device with the stored pivot sequence of the pattern's plan.  None: no plan (yet), a NEP with terms outside its SPMF sum, a
     refusal -- the caller takes the general route."""
     lu_kw = lu_kw or {}
-    if set(lu_kw) - {"expected_solves"} or not _DeviceRefactor.enabled() or env_str("NEP_LU_TERMS", "1") == "0":
+    route = _single_terms_route(nep, lu_kw)
+    if route is None:
         return None
-    from .nep import AbstractSPMF
-    if not (isinstance(nep, AbstractSPMF) and type(nep).compute_Mder is AbstractSPMF.compute_Mder
-            and hasattr(nep, "aligned_terms_dev")):
-        return None
-    if not _DeviceRefactor.plans:
-        return None
-    al = nep.aligned_terms_dev()
-    if al is None:
-        return None
-    indptr, indices, D_dev, G = al
-    plan = _DeviceRefactor.lookup(_DeviceRefactor.key(_Pattern(indptr, indices, (nep.n, nep.n)), (None, None, None)))
-    if plan is None:
-        return None
-    Cf = np.asarray(coef, dtype=np.complex128).reshape(1, -1)
-    normA = np.sqrt(np.maximum(np.einsum("bs,st,bt->b", Cf.conj(), G, Cf).real, 0.0))
-    lu = _DeviceRefactor.factor_batch_terms(plan, nep.n, D_dev, Cf, normA, expected_solves=int(reused(lu_kw)["expected_solves"]))[0]
-    if lu is not None:
-        lu.strategy = dict(plan["strategy"], numeric="device (stored pivot sequence)")
-    return lu
+    return _single_from_row(route, np.asarray(coef, dtype=np.complex128).reshape(1, -1), lu_kw)
 
 
 def seed_plan_from_rank0(nep, lam, group=None, permc_spec=None, wait=True):

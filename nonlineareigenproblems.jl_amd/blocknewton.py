@@ -26,7 +26,7 @@ import torch
 from . import _lib, dense
 from ._lib import lib, check, hptr, c_vp, cd
 from .exceptions import NoConvergenceException
-from .nep import AbstractSPMF, CDT, to_dev, to_host, stream_ptr
+from .nep import CDT, pure_spmf, to_dev, to_host, stream_ptr
 
 EPS = np.finfo(float).eps
 BORDERED = ("eliminate", "whole")
@@ -90,7 +90,7 @@ def update22_tables(S, ds, i, l):
 
 def check_arguments(nep, S, X, bordered, refine, blockprod="fused"):
     """(S, X, n, p) as complex arrays with the reference's defaults (:49-50), or the exception the call deserves"""
-    if not isinstance(nep, AbstractSPMF) or type(nep).compute_MM is not AbstractSPMF.compute_MM:
+    if not pure_spmf(nep, "MM"):
         raise TypeError("blocknewton needs an SPMF-type NEP (sum_t f_t(lam) A_t with compute_MM), not %s" % type(nep).__name__)
     if bordered not in BORDERED:
         raise ValueError("bordered must be one of %r, not %r" % (BORDERED, bordered))

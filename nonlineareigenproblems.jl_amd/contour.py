@@ -13,15 +13,22 @@ i = r (mod P); the only exchange is ONE all-gather of the 2 n k partial block, f
 fixed-order sum so that every rank holds bit-identical A0, A1.
 """
 
+import time
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 import scipy.linalg as sla
+import scipy.sparse as sp
 import torch
 import torch.distributed as dist
 
 from . import dense
 from ._env import env_flag, env_str
+from ._devicelu import GROWTH_UNREFINED
+from ._streams import _eig_streams
 from .errmeasure import DefaultErrmeasure, estimate_errors
-from .linsolvers import BackslashLinSolverCreator, DeviceLU, HostLUPool, create_linsolver, lin_solve, _DeviceRefactor
+from .linsolvers import (BackslashLinSolverCreator, DeviceLU, HostLUPool, create_linsolver, factor_term_rows, lin_solve, terms_route,
+                         _DeviceRefactor, _nep_hostlu)
 from .nep import CDT, to_dev, to_host
 
 EPS = np.finfo(float).eps
@@ -51,83 +58,96 @@ class _DeviceOps:
     scal = staticmethod(dense.scal)
 
 
-_SOLVE_STREAMS = {}
+class _Phases:
+    """info["phases_s"] (a dict the caller put there): wall time of a driver's pieces, each closed by a device synchronisation -- for
+    the record of what is sharded (factorise, solve) and what every rank repeats (the rest), also with one rank.  Without that dict
+    nothing is recorded and nothing synchronises."""
 
-def integrate_interval(ST, f, gv, a, b, N, info=None, ops=_DeviceOps):
-    """returns S with S[j] ~ int f(t) g_j(t) dt  as a device tensor (m, k, n) (m = len(gv)).
-    f(t) returns (X, c): the integrand value is c*X with X a device (k, n) block.
-    `ops` exists so that the sharding / all-gather / fixed-order-sum logic can be exercised by the
-    world_size-2 gloo test on CPU tensors; the drivers always use the HIP kernels."""
-    h = (b - a) / N
-    t = a + h * np.arange(N)
-    m = len(gv)
-    G = np.array([[g(tt) for g in gv] for tt in t], dtype=np.complex128)    # N x m
-    world, rank = 1, 0
-    comm = getattr(ST, "comm", None) if getattr(ST, "sharded", False) else None
-    if comm is not None:
-        world, rank = comm.world, comm.rank
-    elif getattr(ST, "sharded", False) and dist.is_available() and dist.is_initialized():
-        world, rank = dist.get_world_size(), dist.get_rank()
-    S = None
-    mine = range(rank, N, world)
-    # info["phases_s"] (a dict the caller put there): wall time of the pieces, each closed by a device synchronisation -- for the
-    # record of what is sharded (factorise, solve) and what every rank repeats (the rest), also with one rank
-    ph = info.get("phases_s") if (info is not None and isinstance(info.get("phases_s"), dict)) else None
-    import time as _time
+    def __init__(self, info):
+        ph = info.get("phases_s") if info is not None else None
+        self.ph = ph if isinstance(ph, dict) else None
+        self.start()
 
-    def _tick(name, t0):
-        if ph is not None:
-            if torch.cuda.is_available() and (S is None or S.is_cuda):
+    def start(self):
+        self.t0 = time.perf_counter()
+
+    def tick(self, name, block=None):
+        """closes the piece `name`; block: the tensor the piece worked on (a CPU tensor needs no synchronisation)"""
+        if self.ph is not None:
+            if torch.cuda.is_available() and (block is None or block.is_cuda):
                 torch.cuda.synchronize()
-            ph[name] = ph.get(name, 0.0) + _time.perf_counter() - t0
-        return _time.perf_counter()
-    tp = _time.perf_counter()
-    if hasattr(f, "prefetch"):
-        f.prefetch([t[i] for i in mine])
-    tp = _tick("factorise_nodes", tp)
-    # Node solves whose factors are all on the device already (the batched numeric LU): the solve of one node is a chain of ~15 kernels
-    # that do not fill the chip (32 right-hand sides, 0.64 ms per node on gun), and the nodes are independent -- they go round robin
-    # onto two side streams, each result into its own block, and are accumulated on the caller's stream IN NODE ORDER (the sum
-    # is the same, to the bit, as with one stream).
-    nstreams = 2    # measured on C4: 83.0 / 76.9 / 78-110 / 80.2 / 79.2 ms with 1 / 2 / 3 / 4 / 8 streams
-    ready = getattr(f, "ready", None)
-    if nstreams > 1 and ready and torch.cuda.is_available() and all(t[i] in ready for i in mine) and len(mine) > 1:
-        cur = torch.cuda.current_stream()
-        sts = _SOLVE_STREAMS.setdefault(torch.cuda.current_device(), [])
-        if len(sts) < nstreams:
-            # side streams that share a hardware queue with neither the caller's stream nor each other (probed once per process and
-            # device, nep_stream_pair_serializes): the runtime maps streams onto a small pool of queues in creation order, and two
-            # "concurrent" solve streams on ONE queue run one after the other (round 6: 21 instead of 13 ms for the 64 node solves of
-            # C4, depending on which streams the process happened to create before)
-            from .iar import _eig_streams
-            sts[:] = list(_eig_streams(nstreams, others=(cur,)))
-        for s_ in sts[:nstreams]:
-            s_.wait_stream(cur)
-        pend = []
-        for q, i in enumerate(mine):
-            s_ = sts[q % nstreams]
-            with torch.cuda.stream(s_):
-                X, c = f(t[i])
-                ev = torch.cuda.Event(); ev.record(s_)
-            pend.append((i, X, c, ev))
-        for i, X, c, ev in pend:
-            cur.wait_event(ev)
-            if S is None:
-                S = torch.zeros((m,) + tuple(X.shape), dtype=CDT, device=X.device)
-            for j in range(m):
-                ops.axpy(c * G[i, j], X, S[j])
-            X.record_stream(cur)
-        del pend
-    else:
-        for i in mine:
-            X, c = f(t[i])
-            if S is None:
-                S = torch.zeros((m,) + tuple(X.shape), dtype=CDT, device=X.device)
-            for j in range(m):
-                ops.axpy(c * G[i, j], X, S[j])
-    tp = _tick("solve_nodes_and_accumulate", tp)
+            self.ph[name] = self.ph.get(name, 0.0) + time.perf_counter() - self.t0
+        self.start()
+
+
+def _owned_nodes(ST):
+    """(world, rank, comm) of the integrator type ST: rank r of `world` owns the nodes i = r (mod world).  comm: ST's DeviceComm if
+    it carries one; otherwise torch.distributed's default group says who we are (and the exchange makes a DeviceComm on demand)"""
+    sharded = getattr(ST, "sharded", False)
+    comm = getattr(ST, "comm", None) if sharded else None
+    if comm is not None:
+        return comm.world, comm.rank, comm
+    if sharded and dist.is_available() and dist.is_initialized():
+        return dist.get_world_size(), dist.get_rank(), None
+    return 1, 0, None
+
+
+def _accumulate(S, X, c, Gi, ops):
+    """S[j] += c Gi[j] X for the m moments (S is made on the first node)"""
     if S is None:
-        raise ValueError("rank %d owns no quadrature node (N=%d < world size %d)" % (rank, N, world))
+        S = torch.zeros((len(Gi),) + tuple(X.shape), dtype=CDT, device=X.device)
+    for j in range(len(Gi)):
+        ops.axpy(c * Gi[j], X, S[j])
+    return S
+
+
+_SOLVE_STREAMS = {}
+NSTREAMS = 2    # measured on C4: 83.0 / 76.9 / 78-110 / 80.2 / 79.2 ms with 1 / 2 / 3 / 4 / 8 streams
+
+
+def _solve_nodes_side_streams(f, t, mine, G, ops):
+    """Node solves whose factors are all on the device already (the batched numeric LU): the solve of one node is a chain of ~15
+    kernels that do not fill the chip (32 right-hand sides, 0.64 ms per node on gun), and the nodes are independent -- they go round
+    robin onto NSTREAMS side streams, each result into its own block, and are accumulated on the caller's stream IN NODE ORDER (the
+    sum is the same, to the bit, as with one stream)."""
+    cur = torch.cuda.current_stream()
+    sts = _SOLVE_STREAMS.setdefault(torch.cuda.current_device(), [])
+    if len(sts) < NSTREAMS:
+        # side streams from the cache the drivers share (_streams._eig_streams).  Streams MADE by this call were probed (once per
+        # process and device, nep_stream_pair_serializes) to share a hardware queue with neither the caller's stream nor each other:
+        # the runtime maps streams onto a small pool of queues in creation order, and two "concurrent" solve streams on ONE queue run
+        # one after the other (21 instead of 13 ms for the 64 node solves of C4, depending on which streams the process happened
+        # to create before).  Streams the cache held already -- iar's eig streams, after an iar call -- are handed out as they are:
+        # they were probed against that call's streams, not against `cur`, and nothing is guaranteed about their queues.
+        sts[:] = list(_eig_streams(NSTREAMS, others=(cur,)))
+    for s_ in sts[:NSTREAMS]:
+        s_.wait_stream(cur)
+    pend = []
+    for q, i in enumerate(mine):
+        s_ = sts[q % NSTREAMS]
+        with torch.cuda.stream(s_):
+            X, c = f(t[i])
+            ev = torch.cuda.Event(); ev.record(s_)
+        pend.append((i, X, c, ev))
+    S = None
+    for i, X, c, ev in pend:
+        cur.wait_event(ev)
+        S = _accumulate(S, X, c, G[i], ops)
+        X.record_stream(cur)
+    return S
+
+
+def _solve_nodes(f, t, mine, G, ops):
+    """the plain node loop: solve and accumulate node by node on the caller's stream"""
+    S = None
+    for i in mine:
+        X, c = f(t[i])
+        S = _accumulate(S, X, c, G[i], ops)
+    return S
+
+
+def _exchange(ST, S, world, comm, ops):
+    """the sum of the ranks' partial blocks, identical on every rank: (S, the DeviceComm used or None)"""
     if getattr(ST, "sharded", False) and S.is_cuda and (comm is not None or (dist.is_available() and dist.is_initialized())):
         if comm is None:
             from .comm import DeviceComm
@@ -139,8 +159,34 @@ def integrate_interval(ST, f, gv, a, b, N, info=None, ops=_DeviceOps):
         S = torch.zeros_like(S)
         for p in parts:                            # fixed rank order -> identical on every rank
             ops.axpy(1.0, p, S)
+    return S, comm
+
+
+def integrate_interval(ST, f, gv, a, b, N, info=None, ops=_DeviceOps):
+    """returns S with S[j] ~ int f(t) g_j(t) dt  as a device tensor (m, k, n) (m = len(gv)).
+    f(t) returns (X, c): the integrand value is c*X with X a device (k, n) block.
+    `ops` exists so that the sharding / all-gather / fixed-order-sum logic can be exercised by the
+    world_size-2 gloo test on CPU tensors; the drivers always use the HIP kernels."""
+    h = (b - a) / N
+    t = a + h * np.arange(N)
+    G = np.array([[g(tt) for g in gv] for tt in t], dtype=np.complex128)    # N x m
+    world, rank, comm = _owned_nodes(ST)
+    mine = range(rank, N, world)
+    phases = _Phases(info)
+    if hasattr(f, "prefetch"):
+        f.prefetch([t[i] for i in mine])
+    phases.tick("factorise_nodes")
+    ready = getattr(f, "ready", None)
+    if ready and torch.cuda.is_available() and all(t[i] in ready for i in mine) and len(mine) > 1:
+        S = _solve_nodes_side_streams(f, t, mine, G, ops)
+    else:
+        S = _solve_nodes(f, t, mine, G, ops)
+    phases.tick("solve_nodes_and_accumulate", S)
+    if S is None:
+        raise ValueError("rank %d owns no quadrature node (N=%d < world size %d)" % (rank, N, world))
+    S, comm = _exchange(ST, S, world, comm, ops)
     ops.scal(S, h)
-    tp = _tick("exchange_and_sum", tp)
+    phases.tick("exchange_and_sum", S)
     if info is not None:
         info.update(world=world, rank=rank, nodes=len(mine))
         if comm is not None and getattr(comm, "last_exchange_s", None) is not None:
@@ -148,22 +194,86 @@ def integrate_interval(ST, f, gv, a, b, N, info=None, ops=_DeviceOps):
     return S
 
 
+def host_lu_strategy(creator, A):
+    """keyword arguments of the host factorisation of A for `creator`: its own lu_kw, with the UMFPACK-like strategy (symmetric
+    pattern + zero-free diagonal -> MMD_AT_PLUS_A in symmetric mode, else COLAMD) unless the creator names an ordering or a mode"""
+    if creator.permc_spec is None and "symmetric_mode" not in creator.lu_kw:
+        sym = _nep_hostlu.pattern_symmetric(sp.csc_matrix(A))
+        return dict(creator.lu_kw, permc_spec="MMD_AT_PLUS_A" if sym else "COLAMD", symmetric_mode=bool(sym))
+    return dict(creator.lu_kw, permc_spec=creator.permc_spec)
+
+
+def _release_host_result(fut):
+    """a host factorisation that finished but was never turned into a DeviceLU owns a shared-memory block nobody else will unlink
+    (the worker handed ownership to this process): release it"""
+    try:
+        meta = fut.result()
+        if isinstance(meta, dict) and "shm_name" in meta:
+            _nep_hostlu.release_shm(_nep_hostlu.attach_shm(meta))
+    except BaseException:
+        pass
+
+
+class _BeynTrace:
+    """NEP_BEYN_TRACE=1: when the factorisations of one prefetch were submitted and finished, printed as the nodes are consumed"""
+
+    def __init__(self):
+        self.on = env_flag("NEP_BEYN_TRACE")
+        self.t0 = time.perf_counter()
+        self.host_done = []; self.host_meta = []
+        self.t_submitted = 0.0
+
+    def _ms(self):
+        return 1e3 * (time.perf_counter() - self.t0)
+
+    def device_batch(self, ndev, nall):
+        if self.on:
+            print("[beyn trace] %d of %d nodes factorised on the device (batched) at %.0f ms" % (ndev, nall, self._ms()), flush=True)
+
+    def _host_finished(self, fut):
+        self.host_done.append(time.perf_counter() - self.t0)
+        self.host_meta.append(fut.result() if not fut.exception() else {})
+
+    def host_submitted(self, fut):
+        if self.on:
+            fut.add_done_callback(self._host_finished)
+
+    def all_submitted(self):
+        self.t_submitted = time.perf_counter() - self.t0
+
+    def last_solve_issued(self):
+        if not self.on:
+            return
+        hd = sorted(self.host_done)
+        mt_ = [m_ for m_ in self.host_meta if "t_worker" in m_]
+        if mt_:
+            print("[beyn trace] per factorisation in the worker: splu %.1f ms, factor() %.1f ms, whole task %.1f ms (means over %d)"
+                  % (1e3 * np.mean([m_["t_factor"] for m_ in mt_]), 1e3 * np.mean([m_["t_worker_factor_call"] for m_ in mt_]),
+                     1e3 * np.mean([m_["t_worker"] for m_ in mt_]), len(mt_)), flush=True)
+        print("[beyn trace] submitted all at %.0f ms; host factorisations done: first %.0f ms, half %.0f ms, last %.0f ms; "
+              "last block solve issued at %.0f ms" % (1e3 * self.t_submitted, 1e3 * hd[0], 1e3 * hd[len(hd) // 2], 1e3 * hd[-1],
+                                                      self._ms()), flush=True)
+
+
 class _NodeSolve:
     """f(t) = Tv(g(t)) * weight(t), Tv(lam) = lin_solve(create_linsolver(creator, nep, lam+sigma), Vh)
     (method_beyncontour.jl:89-98, method_block_SS.jl:81-86,129-132).  With the default BackslashLinSolverCreator every
-    node needs a NEW host factorisation; `prefetch` starts all factorisations of this rank's nodes in worker processes
-    so that they run concurrently with each other and with the device solves of the nodes already factored."""
+    node needs a NEW factorisation; `prefetch` factorises all nodes of this rank at once on the device where the pattern has a
+    plan, and otherwise starts their host factorisations in worker processes so that they run concurrently with each other and
+    with the device solves of the nodes already factored."""
 
     BUILDERS = 4   # threads turning host factors into device schedules (nep_lu_create releases the GIL)
     AHEAD = 8      # device factorisations built (or being built) ahead of the node being solved
 
     def __init__(self, nep, linsolvercreator, sigma, g, Vd, weight):
         self.nep, self.creator, self.sigma, self.g, self.Vd, self.weight = nep, linsolvercreator, sigma, g, Vd, weight
+        self.ready = {}       # t -> DeviceLU factorised on the device (or the first node of a cold call)
         self.host = {}        # t -> future of the host factorisation (worker process)
         self.built = {}       # t -> future of the DeviceLU (builder thread)
         self.order = []
         self.next = 0
         self.pool = None
+        self.trace = None     # made by prefetch; without one (early return there) ready / built stay empty and no path below asks for it
         self._pattern = None  # csc pattern of M (all nodes share it) when the host path may seed a device plan
 
     def _build(self, host_future, dev):
@@ -188,88 +298,64 @@ class _NodeSolve:
             self.next += 1
 
     def prefetch(self, ts):
+        """device batch, cold first node, or host pool: where the nodes ts are factorised"""
         c = self.creator
-        workers = getattr(c, "workers", None)
-        if not isinstance(c, BackslashLinSolverCreator) or workers == 0 or len(ts) < 2:
+        if not isinstance(c, BackslashLinSolverCreator) or getattr(c, "workers", None) == 0 or len(ts) < 2:
             return
-        from concurrent.futures import ThreadPoolExecutor
         self.pool = ThreadPoolExecutor(max_workers=self.BUILDERS)
-        self.order = list(ts)
-        trace = env_flag("NEP_BEYN_TRACE")
-        if trace:
-            import time as _t
-            self._t0 = _t.perf_counter(); self._host_done = []; self._host_meta = []
-        # ---- all nodes on the GPU in one pass when the pattern has a device-factorisation plan (_devicelu._DeviceRefactor):
-        # one B x m_t by m_t x nnz product for the values, one batched numeric LU (every launch carries all nodes); nodes
-        # whose factorisation is refused with the stored pivot sequence take the host path below
+        self.trace = _BeynTrace()
         self.ready = {}
-        ts_host = list(ts)
-        if (_DeviceRefactor.enabled() and hasattr(self.nep, "aligned_terms_dev") and c.permc_spec is None and not c.lu_kw
-                and not env_flag("NEP_BEYN_HOST_LU")):
-            al = self.nep.aligned_terms_dev()
-            if al is not None:
-                indptr, indices, D_dev, G = al
+        route = None
+        if c.permc_spec is None and not c.lu_kw and not env_flag("NEP_BEYN_HOST_LU"):
+            route = terms_route(self.nep)
+        if route is not None and route.plan is None and len(ts) >= 4 and env_str("NEP_BEYN_COLD_PLAN", "1") != "0":
+            route = self._cold_first_node(ts[0]) or route
+        if route is not None and route.plan is None:
+            self._pattern = route.pattern               # (the first host factorisation that comes back seeds the plan)
+        self._submit_host(self._factor_on_device(route, ts))
 
-                class _Pattern:             # what _DeviceRefactor.key / maybe_start read of a csc matrix
-                    pass
-                A0 = _Pattern(); A0.indptr = indptr; A0.indices = indices; A0.shape = (self.nep.n, self.nep.n)
-                plan = _DeviceRefactor.lookup(_DeviceRefactor.key(A0, (None, None, None)))
-                lu_first = None
-                if plan is None and len(ts) >= 4 and env_str("NEP_BEYN_COLD_PLAN", "1") != "0":
-                    # FIRST call on this sparsity pattern: instead of sending all N nodes to the host-factorisation worker pool (gun,
-                    # N = 64: 0.67 s for the call, most of it the pool's start-up and 64 SuperLU runs) the first node is factorised on
-                    # the host in this process, its device-LU plan is built right away (enumeration on the GPU, ~25 ms) and waited
-                    # for, and the other N - 1 nodes take the batched device factorisation below like every later call
-                    from .linsolvers import DeviceLU
-                    try:
-                        lu_first = DeviceLU(self.nep.compute_Mder(self.g(ts[0]) + self.sigma), expected_solves=1)
-                        _DeviceRefactor.wait()
-                        plan = _DeviceRefactor.lookup(_DeviceRefactor.key(A0, (None, None, None)))
-                    except Exception:
-                        lu_first = None; plan = None          # (singular node, refused plan ...: the host route below handles every node)
-                    if plan is None:
-                        lu_first = None
-                if plan is None:
-                    self._pattern = A0
-                if plan is not None:
-                    # M(lam_b) = sum_t f_t(lam_b) A_t: only the B x m_t coefficients travel, the values are formed on the GPU
-                    fv = self.nep.get_fv()
-                    tsb = list(ts[1:]) if lu_first is not None else list(ts)       # (the first node of a cold call keeps its host factors)
-                    if lu_first is not None:
-                        self.ready[ts[0]] = lu_first
-                    Cf = np.array([[f.derivs(self.g(t) + self.sigma, 1)[0] for f in fv] for t in tsb], dtype=np.complex128)
-                    normA = np.sqrt(np.maximum(np.einsum("bs,st,bt->b", Cf.conj(), G, Cf).real, 0.0))
-                    lus = _DeviceRefactor.factor_batch_terms(plan, self.nep.n, D_dev, Cf, normA, expected_solves=1,
-                                                             growth=_DeviceRefactor.GROWTH_UNREFINED)
-                    ts_host = []
-                    for t, lu in zip(tsb, lus):
-                        if lu is None:
-                            ts_host.append(t)
-                        else:
-                            self.ready[t] = lu
-                    if trace:
-                        print("[beyn trace] %d of %d nodes factorised on the device (batched) at %.0f ms" %
-                              (len(self.ready), len(ts), 1e3 * (_t.perf_counter() - self._t0)), flush=True)
-        self.order = list(ts_host)
-        strat = None
-        for t in ts_host:
+    def _factor_on_device(self, route, ts):
+        """all nodes on the GPU in one pass when the pattern has a device-factorisation plan (_devicelu._DeviceRefactor): M(lam_b) =
+        sum_t f_t(lam_b) A_t, only the B x m_t coefficients travel, one batched numeric LU (every launch carries all nodes).  Fills
+        `ready`; returns the nodes left for the host: those whose factorisation is refused with the stored pivot sequence, or all"""
+        if route is None or route.plan is None:
+            return list(ts)
+        tsb = [t for t in ts if t not in self.ready]       # (the first node of a cold call keeps its host factors)
+        fv = self.nep.get_fv()
+        Cf = np.array([[f.derivs(self.g(t) + self.sigma, 1)[0] for f in fv] for t in tsb], dtype=np.complex128)
+        lus = factor_term_rows(route, Cf, expected_solves=1, growth=GROWTH_UNREFINED)
+        self.ready.update((t, lu) for t, lu in zip(tsb, lus) if lu is not None)
+        self.trace.device_batch(len(self.ready), len(ts))
+        return [t for t, lu in zip(tsb, lus) if lu is None]
+
+    def _cold_first_node(self, t0):
+        """FIRST call on this sparsity pattern: instead of sending all N nodes to the host-factorisation worker pool (gun, N = 64:
+        0.67 s for the call, most of it the pool's start-up and 64 SuperLU runs) the first node is factorised on the host in this
+        process, its device-LU plan is built right away (enumeration on the GPU, ~25 ms) and waited for, and the other N - 1 nodes
+        take the batched device factorisation like every later call.  Returns the route with its plan, the node in `ready`; None
+        where that did not work (singular node, refused plan ...: the host route handles every node)"""
+        try:
+            lu = DeviceLU(self.nep.compute_Mder(self.g(t0) + self.sigma), expected_solves=1)
+            _DeviceRefactor.wait()
+            route = terms_route(self.nep)
+        except Exception:
+            return None
+        if route is None or route.plan is None:
+            return None
+        self.ready[t0] = lu
+        return route
+
+    def _submit_host(self, ts):
+        """host factorisations of the nodes ts in the worker pool, their uploads in the builder threads"""
+        self.order = list(ts)
+        kw = None
+        for t in ts:
             A = self.nep.compute_Mder(self.g(t) + self.sigma)
-            if strat is None:
-                # UMFPACK-like strategy (symmetric pattern + zero-free diagonal?) decided ONCE: all nodes share one pattern
-                import nep_amd_hostlu as hl
-                import scipy.sparse as sp_
-                kw0 = dict(c.lu_kw)
-                if c.permc_spec is None and "symmetric_mode" not in kw0:
-                    sym = hl.pattern_symmetric(sp_.csc_matrix(A))
-                    strat = dict(permc_spec="MMD_AT_PLUS_A" if sym else "COLAMD", symmetric_mode=bool(sym))
-                else:
-                    strat = dict(permc_spec=c.permc_spec)
-            self.host[t] = HostLUPool.submit(A, workers=workers, **dict(c.lu_kw, **strat))
-            if trace:
-                self.host[t].add_done_callback(lambda f, s=self: (s._host_done.append(_t.perf_counter() - s._t0),
-                                                                   s._host_meta.append(f.result() if not f.exception() else {})))
-        if trace:
-            self._t_submitted = _t.perf_counter() - self._t0
+            if kw is None:
+                kw = host_lu_strategy(self.creator, A)         # decided ONCE: all nodes share one pattern
+            self.host[t] = HostLUPool.submit(A, workers=getattr(self.creator, "workers", None), **kw)
+            self.trace.host_submitted(self.host[t])
+        self.trace.all_submitted()
         self._submit_builds()
 
     def close(self):
@@ -278,26 +364,15 @@ class _NodeSolve:
                 f.cancel()
             self.pool.shutdown(wait=True)
             self.pool = None
-            # host factorisations that finished (or still finish) but were never turned into a DeviceLU own a shared-memory
-            # block nobody else will unlink (the worker handed ownership to this process): release it
-            import nep_amd_hostlu as hl
-
-            def _release(fut):
-                try:
-                    meta = fut.result()
-                    if isinstance(meta, dict) and "shm_name" in meta:
-                        hl.release_shm(hl.attach_shm(meta))
-                except BaseException:
-                    pass
-            for f in self.host.values():
+            for f in self.host.values():               # (finished, or still finishing)
                 if f.done():
-                    _release(f)
+                    _release_host_result(f)
                 else:
-                    f.add_done_callback(_release)
+                    f.add_done_callback(_release_host_result)
             self.built.clear(); self.host.clear()
 
     def __call__(self, t):
-        if t in getattr(self, "ready", {}):
+        if t in self.ready:
             lu = self.ready.pop(t)
             X = lu.solve(self.Vd)
             if not self.ready and not self.built and self.next >= len(self.order):
@@ -312,27 +387,22 @@ class _NodeSolve:
                 self.close()
                 raise
             if not self.built and self.next >= len(self.order):
-                if env_flag("NEP_BEYN_TRACE"):
-                    import time as _t
-                    hd = sorted(self._host_done)
-                    mt_ = [m_ for m_ in self._host_meta if "t_worker" in m_]
-                    if mt_:
-                        print("[beyn trace] per factorisation in the worker: splu %.1f ms, factor() %.1f ms, whole task %.1f ms (means over %d)"
-                              % (1e3 * np.mean([m_["t_factor"] for m_ in mt_]), 1e3 * np.mean([m_["t_worker_factor_call"] for m_ in mt_]),
-                                 1e3 * np.mean([m_["t_worker"] for m_ in mt_]), len(mt_)), flush=True)
-                    print("[beyn trace] submitted all at %.0f ms; host factorisations done: first %.0f ms, half %.0f ms, last %.0f ms; "
-                          "last block solve issued at %.0f ms" % (1e3 * self._t_submitted, 1e3 * hd[0], 1e3 * hd[len(hd) // 2], 1e3 * hd[-1],
-                                                                  1e3 * (_t.perf_counter() - self._t0)), flush=True)
+                self.trace.last_solve_issued()
                 self.close()
             return X, self.weight(t)
         M0inv = create_linsolver(self.creator, self.nep, self.g(t) + self.sigma)
         return lin_solve(M0inv, self.Vd), self.weight(t)
 
 
-def _beyn_tail_device(S, n, k, rank_drop_tol):
-    """the dense tail of Beyn's method with the n x k moments left on the device (see contour_beyn).  S: device (2, k, n) block of the
-    UNSCALED moments (A_j = S[j] / (2 pi i)).  Returns (singular values of A0, rank p, B (p x p, host), Q (device (k, n)), U_R[:, :p])
-    or None when the device QR met a breakdown (the caller then takes the host route)."""
+def _beyn_tail_device(S, n, k):
+    """the device part of Beyn's dense tail.  The moments stay on the device (method_beyncontour.jl:114-128 needs only k x k pieces of
+    them on the host): A0 = Q R by column-wise DGKS on the device (K6; the columns A0 has beyond its rank become orthonormalised noise,
+    R shows the rank), svd(R) on the host (k x k) gives the singular values of A0 and V = Q U_R; B = V0^H A1 W0 S^-1 = U_R^H (Q^H A1) W0
+    S^-1 with the k x k Gram block Q^H A1 from the device; the eigenvectors V0 VB = Q (U_R VB) by K7.  Downloaded: two k x (k + 2) blocks
+    instead of two n x k ones; the n x k SVD (9 ms of host LAPACK on gun, repeated by every rank) is gone.
+    S: device (2, k, n) block of the UNSCALED moments (A_j = S[j] / (2 pi i)).  Returns (oh, G, Q): the k x (k + 2) rows
+    nep_orth_qr_dev wrote (row j: R[:j, j], the real R[j, j], the flags of column j in the imaginary part of entry j + 1), the k x k
+    Gram block Q^H S[1] (host), Q as a device (k, n) tensor."""
     Qd = S[0].clone()                                      # (k, n) = column-major n x k; orthonormalised in place, column by column
     from ._lib import lib, check, c_vp, cd
     from .nep import stream_ptr
@@ -343,13 +413,20 @@ def _beyn_tail_device(S, n, k, rank_drop_tol):
     # G = Q^H S[1] (k x k, column-major) on the library's own GEMM, the n-long reduction split over `ksplit` workgroups
     check(lib.nep_zgemm_sk(2, 0, k, k, n, cd(1.0), c_vp(Qd.data_ptr()), n, c_vp(S[1].data_ptr()), n, cd(0.0), c_vp(Gd.data_ptr()), k, ksplit,
                            c_vp(work.data_ptr()), stream_ptr()))
-    bh = buf[:k * (k + 2) + k * k].cpu().numpy()             # ONE download: k (k + 2) + k^2 numbers
-    oh = bh[:k * (k + 2)].reshape(k, k + 2)
-    G = bh[k * (k + 2):].reshape(k, k).T                    # Gd[c, r] = G[r, c]
+    bh = buf[:k * (k + 2) + k * k].cpu().numpy()
+    return bh[:k * (k + 2)].reshape(k, k + 2), bh[k * (k + 2):].reshape(k, k).T, Qd            # (Gd[c, r] = G[r, c])
+
+
+def beyn_tail_from_qr(oh, G, rank_drop_tol):
+    """host part of the device tail: (singular values of A0, rank p, B (p x p), U_R[:, :p]) from the rows `oh` of the device QR of
+    the unscaled A0 and G = Q^H (unscaled A1); the eigenvector basis is V0 = Q U_R[:, :p].  None when the QR cannot be trusted (the
+    caller then takes the host route)."""
+    k = oh.shape[0]
+    flags = [int(oh[j, j + 1].imag) for j in range(k)]
+    if any(f & 2 for f in flags):                           # breakdown flag (||w|| = 0 or not finite)
+        return None
     R = np.zeros((k, k), dtype=np.complex128)
     for j in range(k):
-        if int(oh[j, j + 1].imag) & 2:                      # breakdown flag (||w|| = 0 or not finite)
-            return None
         R[:j, j] = oh[j, :j]
         R[j, j] = oh[j, j].real
     # svd(R) = svd(A0) and V = Q U_R hold for an ORTHONORMAL Q only.  A column whose last enqueued DGKS pass still met the
@@ -357,16 +434,38 @@ def _beyn_tail_device(S, n, k, rank_drop_tol):
     # rank deficient by design: R[j, j] at round-off of R[0, 0]), not for one that carries weight -- the host route then (svd of the
     # downloaded block, as the reference does it)
     r00 = abs(R[0, 0]) if k else 0.0
-    for j in range(k):
-        if (int(oh[j, j + 1].imag) & 1) and abs(R[j, j]) > 1e-10 * r00:
-            return None
+    if any((flags[j] & 1) and abs(R[j, j]) > 1e-10 * r00 for j in range(k)):
+        return None
     c = 1.0 / (2j * np.pi)
     Ur, Sv, Wh = sla.svd(R * c)                             # A0 = Q (R / (2 pi i)): same singular values, V = Q U_R
     p = int(np.sum(Sv / Sv[0] > rank_drop_tol))
     W0 = Wh.conj().T[:, :p]
     UrP = Ur[:, :p]
     B = (UrP.conj().T @ (G * c) @ W0) @ np.diag(1.0 / Sv[:p])
-    return Sv, p, B, Qd, UrP
+    return Sv, p, B, UrP
+
+
+def beyn_tail_host(A0, A1, rank_drop_tol):
+    """the reference's tail (method_beyncontour.jl:114-128) on the downloaded moments: (singular values of A0, rank p, B, V0)"""
+    V, Sv, Wh = sla.svd(A0, full_matrices=False)
+    W = Wh.conj().T
+    p = int(np.sum(Sv / Sv[0] > rank_drop_tol))
+    V0 = V[:, :p]; W0 = W[:, :p]
+    B = (V0.conj().T @ A1 @ W0) @ np.diag(1.0 / Sv[:p])
+    return Sv, p, B, V0
+
+
+def select_eigenpairs(lam, errs, tol, sigma, radius, neigs):
+    """indices of the pairs contour_beyn returns, in its order: those with errs < tol, nearest to sigma first, those inside the
+    ellipse (semi-axes `radius` around sigma) before the others, at most neigs.  errs None (sanity_check=False): all, in that order."""
+    good = np.arange(len(lam)) if errs is None else np.nonzero(errs < tol)[0]
+    sgi = good[np.argsort(abs(sigma - lam[good]), kind="stable")]
+    d = lam[sgi] - sigma
+    inside = (d.real / radius[0]) ** 2 + (d.imag / radius[1]) ** 2 <= 1
+    sel = sgi[np.argsort(~inside, kind="stable")]
+    if errs is not None and len(sel) > neigs:
+        sel = sel[:neigs]
+    return sel
 
 
 def probe_block(n, k, seed=10):
@@ -399,84 +498,45 @@ def contour_beyn(nep, MIntegrator=MatrixTrapezoidal, tol=np.sqrt(EPS), sigma=0.0
         raise ValueError("Cannot compute more eigenvalues than the size of the NEP with contour_beyn() k=%d n=%d" % (k, n))
     if k <= 0:
         raise ValueError("k must be positive, k=%d." % k)
-    import time as _time
-    ph = info.get("phases_s") if (info is not None and isinstance(info.get("phases_s"), dict)) else None
-
-    def _tick(name, t0):
-        if ph is not None:
-            torch.cuda.synchronize()
-            ph[name] = ph.get(name, 0.0) + _time.perf_counter() - t0
-        return _time.perf_counter()
-    tp = _time.perf_counter()
+    phases = _Phases(info)
     if Vh is None:
         Vh = probe_block(n, k)
     Vd = to_dev(Vh)
-    tp = _tick("probe_generate_and_upload", tp)
+    phases.tick("probe_generate_and_upload")
 
     f = _NodeSolve(nep, linsolvercreator, sigma, g, Vd, gp)
-
     S = integrate_interval(MIntegrator, f, [lambda s: 1.0 + 0j, g], 0.0, 2 * np.pi, N, info=info)
-    tp = _time.perf_counter()
-    dev_tail = (S.is_cuda and k >= 2 and env_str("NEP_BEYN_DEVICE_TAIL", "1") != "0")
-    A0 = A1 = None
-    lam = None
-    if dev_tail:
-        # The moments stay on the device (method_beyncontour.jl:114-128 needs only k x k pieces of them on the host): A0 = Q R by
-        # column-wise DGKS on the device (K6; the columns A0 has beyond its rank become orthonormalised noise, R shows the rank),
-        # svd(R) on the host (k x k) gives the singular values of A0 and V = Q U_R; B = V0^H A1 W0 S^-1 = U_R^H (Q^H A1) W0 S^-1 with
-        # the k x k Gram block Q^H A1 from the device; the eigenvectors V0 VB = Q (U_R VB) by K7.  Downloaded: two k x (k + 2)
-        # blocks instead of two n x k ones; the n x k SVD (9 ms of host LAPACK on gun, repeated by every rank) is gone.
-        got = _beyn_tail_device(S, n, k, rank_drop_tol)
-        if got is not None:
-            Sv, p, B, Qd, UrP = got
-            lam, VB = sla.eig(B)
-            lam = lam + sigma
-            tp = _tick("svd_and_eig_host", tp)
-            QT = dense.gemm_ts(Qd, UrP @ VB, rowmajor=True)        # (n, p) row-major
-            tp = _tick("eigenvectors", tp)
-            if info is not None and info.get("moments", True):      # (a caller that wants them; bench.py's timed call opts out)
-                A0 = to_host(S[0]) / (2j * np.pi); A1 = to_host(S[1]) / (2j * np.pi)
-    if lam is None:
+    phases.start()
+    A0 = A1 = tail = Qd = None
+    if S.is_cuda and k >= 2 and env_str("NEP_BEYN_DEVICE_TAIL", "1") != "0":
+        oh, G, Qd = _beyn_tail_device(S, n, k)
+        tail = beyn_tail_from_qr(oh, G, rank_drop_tol)
+    if tail is None:
+        Qd = None
         A0 = to_host(S[0]) / (2j * np.pi)
         A1 = to_host(S[1]) / (2j * np.pi)
-        tp = _tick("moments_download", tp)
-        V, Sv, Wh = sla.svd(A0, full_matrices=False)
-        W = Wh.conj().T
-        p = int(np.sum(Sv / Sv[0] > rank_drop_tol))
-        V0 = V[:, :p]; W0 = W[:, :p]
-        B = (V0.conj().T @ A1 @ W0) @ np.diag(1.0 / Sv[:p])
-        lam, VB = sla.eig(B)
-        lam = lam + sigma
-        tp = _tick("svd_and_eig_host", tp)
-        # eigenvectors V0*VB on the device (K7), normalised
-        V0d = to_dev(V0)
-        QT = dense.gemm_ts(V0d, VB, rowmajor=True)                 # (n, p) row-major
-        tp = _tick("eigenvectors", tp)
+        phases.tick("moments_download")
+        tail = beyn_tail_host(A0, A1, rank_drop_tol)
+    Sv, p, B, U = tail
+    lam, VB = sla.eig(B)
+    lam = lam + sigma
+    phases.tick("svd_and_eig_host")
+    # eigenvectors V0 VB on the device (K7), (n, p) row-major: V0 = Q U_R[:, :p] after the device tail, the uploaded V0 otherwise
+    QT = dense.gemm_ts(Qd, U @ VB, rowmajor=True) if Qd is not None else dense.gemm_ts(to_dev(U), VB, rowmajor=True)
+    phases.tick("eigenvectors")
+    if Qd is not None and info is not None and info.get("moments", True):      # (a caller that wants them; bench.py's timed call opts out)
+        A0 = to_host(S[0]) / (2j * np.pi); A1 = to_host(S[1]) / (2j * np.pi)
     if info is not None:
         info.update(p=p, S=Sv, A0=A0, A1=A1)
-
-    def inside(l):
-        return ((l - sigma).real / radius[0]) ** 2 + ((l - sigma).imag / radius[1]) ** 2 <= 1
-
-    def cols(sel):
-        Q = to_host(dense.rowmajor_to_cols(QT, np.asarray(sel, dtype=np.int32)))
-        return Q / np.linalg.norm(Q, axis=0)[None, :] if Q.shape[1] else Q
-
-    if not sanity_check:
-        si = np.argsort(abs(sigma - lam), kind="stable")
-        perm = np.argsort(~inside(lam[si]), kind="stable")
-        return lam[si[perm]], cols(si[perm])
-    errs = estimate_errors(errmeasure, lam, QT)
-    tp = _tick("residual_filter", tp)
-    good = np.nonzero(errs < tol)[0]
-    sgi = good[np.argsort(abs(sigma - lam[good]), kind="stable")]
-    perm = np.argsort(~inside(lam[sgi]), kind="stable")
-    sel = sgi[perm]
-    if len(sel) > neigs:
-        sel = sel[:neigs]
-    if info is not None:
-        info.update(errs=errs)
-    return lam[sel], cols(sel)
+    errs = None
+    if sanity_check:
+        errs = estimate_errors(errmeasure, lam, QT)
+        phases.tick("residual_filter")
+        if info is not None:
+            info.update(errs=errs)
+    sel = select_eigenpairs(lam, errs, tol, sigma, radius, neigs)
+    Q = to_host(dense.rowmajor_to_cols(QT, np.asarray(sel, dtype=np.int32)))
+    return lam[sel], (Q / np.linalg.norm(Q, axis=0)[None, :] if Q.shape[1] else Q)
 
 
 def probe_block_uniform(n, L, seed=10):

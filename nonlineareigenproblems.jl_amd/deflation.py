@@ -35,7 +35,7 @@ import torch
 from . import _lib, dense, funcs
 from ._lib import lib, check, hptr, c_vp
 from .nep import (NEP, AbstractSPMF, SPMF_NEP, SumNEP, LowRankMatrixAndFunction, LowRankFactorizedNEP, CDT, to_dev, to_host,
-                  is_dev, stream_ptr)
+                  is_dev, pure_spmf, stream_ptr)
 
 MODES = ("Auto", "Generic", "SPMF", "MM")
 MAX_P, MAX_K = 32, 64              # limits of nep_defl_expand (include/nepmi355.h)
@@ -251,7 +251,7 @@ class DeflatedGenericNEP(_DeflatedMMBase):
         if not self._expand_fused(Vd, a, G, W, s, Vn, zb):
             self._expand_composed(Vd, a, G, W, s, Vn, zb)
         org = self.orgnep
-        if isinstance(org, AbstractSPMF) and type(org).compute_Mlincomb is AbstractSPMF.compute_Mlincomb:
+        if pure_spmf(org, "Mlincomb"):
             org.dev.mlincomb(org.coeff_block(lam, np.ones(K)), Vn, z)                # K1 writes the first n0 entries of z
         else:
             dense.copy(org.compute_Mlincomb(lam, Vn), z, self.n0)

@@ -114,10 +114,9 @@ class ArnoldiEigSolver(EigSolver):
 
     @staticmethod
     def accepts(nep):
-        """the purity test of lu_from_terms, and sparse matrices"""
-        from .nep import AbstractSPMF
-        return (isinstance(nep, AbstractSPMF) and type(nep).compute_Mder is AbstractSPMF.compute_Mder
-                and type(nep).compute_Mlincomb is AbstractSPMF.compute_Mlincomb and hasattr(nep, "aligned_terms_dev")
+        """a pure SPMF (nep.pure_spmf) with sparse matrices"""
+        from .nep import pure_spmf
+        return (pure_spmf(nep, "Mder", "Mlincomb") and hasattr(nep, "aligned_terms_dev")
                 and nep.issparse() and nep._aligned_terms() is not None)
 
     # ---- C = tau B - A = sum_t (tau cB_t - cA_t) A_t

@@ -33,10 +33,11 @@ from ._env import env_flag, env_float, env_int, env_str
 from ._lib import (lib, check, c_vp, c_i32, hptr, cdouble, NepError, IarOpts, IarResult, FV_EVAL, NEP_ERR_BREAKDOWN, NEP_ERR_RETRY,
                    NEP_ERR_NOCONV)
 from ._ritzchecks import RitzChecks
+from ._streams import _check_stream, _eig_streams
 from .errmeasure import (DefaultErrmeasure, ResidualErrmeasure, StandardSPMFErrmeasure, estimate_errors, estimate_errors_async)
 from .exceptions import NoConvergenceException
 from .linsolvers import DefaultLinSolverCreator, FactorizeLinSolver, create_linsolver
-from .nep import CDT, AbstractSPMF, to_host, to_host_cm, stream_ptr
+from .nep import CDT, AbstractSPMF, pure_spmf, to_host, to_host_cm, stream_ptr
 
 EPS = np.finfo(float).eps
 
@@ -96,56 +97,7 @@ iar.dev_eig_fallbacks = 0            # checks whose device eigen-decomposition r
 iar.last_route = None                # the pipeline the last call took (_route; diagnostics, tests)
 
 
-_CHECK_STREAMS = {}
-
-
-def _check_stream():
-    dev = torch.cuda.current_device()
-    st = _CHECK_STREAMS.get(dev)
-    if st is None:
-        # the convergence checks are off the critical path: their stream asks for the LOWEST priority the device offers, so that
-        # the dispatcher serves the recurrence's kernels first when both streams have work (torch clamps to the device's
-        # range, a lower number is a higher priority)
-        st = _CHECK_STREAMS[dev] = torch.cuda.Stream(priority=1)
-    return st
-
-
-_EIG_STREAMS = {}
 _EIG_WORK = {}
-
-
-def _eig_streams(count, others=()):
-    """streams for the device eigen-decompositions (3 ms one-wavefront kernels) that overlap with the streams in `others`
-    (the recurrence's and the checks').  The runtime maps streams onto a small pool of hardware queues and gives no way to ask
-    which; two streams on one queue serialise (measured: the convergence checks queued 4 ms per batch behind the
-    decompositions).  So candidates are probed (nep_stream_pair_serializes, ~1.5 ms each, once per process and device) and the
-    first ones that serialise with none of `others` nor with each other are kept."""
-    dev = torch.cuda.current_device()
-    sts = _EIG_STREAMS.setdefault(dev, [])
-    if len(sts) >= count:
-        return sts[:count]
-    cands = [torch.cuda.Stream(priority=0) for _ in range(8)]
-    for c in cands:
-        if len(sts) >= count:
-            break
-        ok = True
-        for o in list(others) + sts:
-            r = c_i32(0)
-            check(lib.nep_stream_pair_serializes(c_vp(o.cuda_stream), c_vp(c.cuda_stream), _C.byref(r)))
-            if r.value:
-                ok = False
-                break
-        if ok:
-            sts.append(c)
-    while len(sts) < count:              # no free hardware queue: better a shared one than none
-        sts.append(cands[len(sts) % len(cands)])
-        _eig_streams.shared = True
-    return sts[:count]
-
-
-_eig_streams.shared = False
-
-
 _EIG_WORK_LOCK = threading.Lock()
 _EIG_WORK_KEEP = 2          # idle blocks kept per device (260 MB each at m = 100); more concurrent calls allocate and free their own
 
@@ -186,8 +138,7 @@ def _native_errmeasure(errmeasure, nep):
 
 def _plain_spmf(nep):
     """an SPMF operator whose products are the base class's own: what the native step and the one-call run compute themselves"""
-    return (isinstance(nep, AbstractSPMF) and type(nep).lincomb_rowscale is AbstractSPMF.lincomb_rowscale
-            and type(nep).compute_Mlincomb is AbstractSPMF.compute_Mlincomb)
+    return pure_spmf(nep, "Mlincomb") and type(nep).lincomb_rowscale is AbstractSPMF.lincomb_rowscale
 
 
 def _device_lu(M0inv):

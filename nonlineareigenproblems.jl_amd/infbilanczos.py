@@ -20,12 +20,12 @@ from ._lib import lib, check, hptr, c_vp, NepError, NEP_ERR_UNSUPPORTED
 from .errmeasure import DefaultErrmeasure, estimate_errors
 from .exceptions import NoConvergenceException
 from .linsolvers import lin_solve
-from .nep import AbstractSPMF, CDT, to_dev, dptr, stream_ptr
+from .nep import CDT, pure_spmf, to_dev, dptr, stream_ptr
 from .twosided import twosided_linsolvers
 
 
 def _standard_spmf(nep):
-    return isinstance(nep, AbstractSPMF) and type(nep).compute_Mlincomb is AbstractSPMF.compute_Mlincomb
+    return pure_spmf(nep, "Mlincomb")
 
 
 def taylor_table(nep, sigma, m):

@@ -21,7 +21,7 @@ import torch
 from . import _lib
 from ._env import env_str
 from ._lib import lib, check, hptr, c_vp
-from .nep import CDT, to_dev, to_host, is_dev, stream_ptr
+from .nep import CDT, to_dev, to_host, is_dev, pure_spmf, stream_ptr
 
 
 class LinSolver:
@@ -33,8 +33,8 @@ class LinSolverCreator:
 
 
 from ._hostlu_pool import HostLUPool, _nep_hostlu  # noqa: E402,F401
-from ._devicelu import (DeviceLU, _DeviceRefactor, _Pattern, host_factor, lu_from_terms, reused,  # noqa: E402,F401
-                        seed_plan_from_rank0)
+from ._devicelu import (DeviceLU, _DeviceRefactor, _Pattern, factor_term_rows, host_factor, lu_from_terms, reused,  # noqa: E402,F401
+                        seed_plan_from_rank0, terms_route)
 from ._refine import EPS, GO, TAKE_BACK, Refine, rule_step  # noqa: E402,F401
 from ._gmres import GMRESLinSolver, GMRESLinSolverCreator  # noqa: E402
 
@@ -92,8 +92,7 @@ class FactorizeLinSolver(LinSolver):
                 self._cabs = np.ascontiguousarray(np.abs(cf))
                 self._spmf = nep.dev.h
                 # pure SPMF operator (compute_Mlincomb not overridden): M x is formed inside the criterion kernel
-                from .nep import AbstractSPMF
-                self._cf = cf if type(nep).compute_Mlincomb is AbstractSPMF.compute_Mlincomb else None
+                self._cf = cf if pure_spmf(nep, "Mlincomb") else None
 
     def _residual(self, b, want_omega):
         """W[0] = b - M(lam) x  (x = W[1]); returns the backward error (None if not requested)."""

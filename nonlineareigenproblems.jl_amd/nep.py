@@ -555,11 +555,7 @@ class AbstractSPMF(NEP):
                 D[pos, t] = M.data
             indices = (keyU % n).astype(np.int32)
             indptr = np.concatenate(([0], np.cumsum(np.bincount(keyU // n, minlength=n)))).astype(np.int32)
-
-            class _U:                                                      # the three attributes the caller reads
-                pass
-            U = _U(); U.indptr = indptr; U.indices = indices
-            self._aligned = (U.indptr.copy(), U.indices.copy(), D)
+            self._aligned = (indptr, indices, D)
         return self._aligned
 
     def compute_MM(self, S, V):
@@ -655,11 +651,19 @@ class AbstractSPMF(NEP):
         return self._fro
 
 
+def pure_spmf(nep, *ops):
+    """nep is an AbstractSPMF whose compute_<op> methods (ops from "Mlincomb", "Mder", "MM") are AbstractSPMF's own: M(lam) is
+    exactly its SPMF sum as far as those operations go, no part outside the terms (the dense corner of the waveguide problem)"""
+    cls = type(nep)
+    return isinstance(nep, AbstractSPMF) and all(getattr(cls, "compute_" + op) is getattr(AbstractSPMF, "compute_" + op)
+                                                 for op in ops)
+
+
 def require_pure_spmf(nep, who):
     """drivers that feed their own coefficient blocks to the stacked-CSR kernels (nleigs, iar_chebyshev, ilan) are only
     correct when M(lam) is exactly its SPMF sum; NEP types with extra terms (the dense corner of the waveguide problem) are
     refused loudly instead of being solved without them"""
-    if not isinstance(nep, AbstractSPMF) or type(nep).compute_Mlincomb is not AbstractSPMF.compute_Mlincomb:
+    if not pure_spmf(nep, "Mlincomb"):
         raise NotImplementedError("%s: the operator has terms outside its SPMF matrices (type %s); use iar / tiar / resinv / "
                                   "quasinewton / augnewton, which go through the NEP's own compute_Mlincomb" % (who, type(nep).__name__))
 
@@ -821,9 +825,8 @@ def _csc_keys(M, n):
 
 
 def _interp_table_route_ok(orgnep):
-    """a pure SPMF (no terms outside its matrices: the purity test of lu_from_terms) with sparse matrices, at most 64 of them"""
-    return (isinstance(orgnep, AbstractSPMF) and type(orgnep).compute_Mder is AbstractSPMF.compute_Mder
-            and type(orgnep).compute_Mlincomb is AbstractSPMF.compute_Mlincomb and orgnep.issparse()
+    """a pure SPMF (no terms outside its matrices: pure_spmf) with sparse matrices, at most 64 of them"""
+    return (pure_spmf(orgnep, "Mder", "Mlincomb") and orgnep.issparse()
             and len(orgnep.get_fv()) <= INTERP_MAX and orgnep._aligned_terms() is not None)
 
 

@@ -13,7 +13,7 @@ from ._lib import lib, check, hptr, c_vp
 from .errmeasure import DefaultErrmeasure, estimate_error
 from .exceptions import NoConvergenceException
 from .linsolvers import DefaultLinSolverCreator, create_linsolver
-from .nep import CDT, to_dev, to_host, stream_ptr
+from .nep import CDT, pure_spmf, to_dev, to_host, stream_ptr
 
 EPS = np.finfo(float).eps
 
@@ -35,9 +35,8 @@ class ScalarNewtonInnerSolver:
 def _mder_times(nep, lam, vb, out, der):
     """out = M^(der)(lam) v on the device: the stacked-CSR kernel K1 directly for pure SPMF operators, the NEP's own
     compute_Mlincomb for types with extra terms (the dense corner of the waveguide problem)"""
-    from .nep import AbstractSPMF
     one = np.ones(1)
-    if type(nep).compute_Mlincomb is AbstractSPMF.compute_Mlincomb:
+    if pure_spmf(nep, "Mlincomb"):
         nep.dev.mlincomb(nep.coeff_block(lam, one, der), vb, out)
     else:
         dense.copy(nep.compute_Mlincomb(lam, vb, a=one, startder=der), out, vb.shape[-1])
@@ -50,11 +49,10 @@ def _host_vec(x):
 
 def rf_forms_ok(nep):
     """the bilinear forms determine y^H M(lam) x: an SPMF with nothing outside its matrices (or the projection of one)"""
-    from .nep import AbstractSPMF
     from .projection import Proj_SPMF_NEP
     if isinstance(nep, Proj_SPMF_NEP):
         return nep.nep_proj is not None
-    return isinstance(nep, AbstractSPMF) and type(nep).compute_Mlincomb is AbstractSPMF.compute_Mlincomb
+    return pure_spmf(nep, "Mlincomb")
 
 
 def spmf_forms(nep, y, x):

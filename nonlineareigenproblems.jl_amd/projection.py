@@ -16,7 +16,7 @@ import torch
 
 from . import dense
 from .exceptions import NoConvergenceException
-from .nep import AbstractSPMF, CDT, ChebPEP, DEP, PEP, SPMF_NEP, is_dev, to_dev
+from .nep import AbstractSPMF, CDT, ChebPEP, DEP, PEP, SPMF_NEP, is_dev, pure_spmf, to_dev
 
 EPS = np.finfo(float).eps
 
@@ -40,7 +40,7 @@ class Proj_SPMF_NEP:
     def __init__(self, orgnep, maxsize=None):
         if not isinstance(orgnep, AbstractSPMF):
             raise TypeError("create_proj_NEP needs an AbstractSPMF")
-        if type(orgnep).compute_Mlincomb is not AbstractSPMF.compute_Mlincomb:
+        if not pure_spmf(orgnep, "Mlincomb"):
             raise NotImplementedError("the operator has terms outside its SPMF matrices (e.g. the waveguide corner block)")
         self.orgnep = orgnep
         self.orgnep_Av = orgnep.get_Av()

@@ -15,7 +15,7 @@ from .errmeasure import DefaultErrmeasure, estimate_error
 from .exceptions import NoConvergenceException
 from .linsolvers import (LinSolver, DeviceLU, FactorizeLinSolver, FactorizeLinSolverCreator, BackslashLinSolverCreator,
                          create_linsolver, lin_solve)
-from .nep import AbstractSPMF, to_dev, to_host
+from .nep import pure_spmf, to_dev, to_host
 from .newton import compute_rf, _mder_times
 
 EPS = np.finfo(float).eps
@@ -51,11 +51,8 @@ def transpose_relation(nep, nept, sigma=None, orders=1):
     """"T" when nept.A_i == A_i^T for every term, "H" when nept.A_i == A_i^H (and not "T"), None otherwise.  Both must be SPMF
     problems with the same number of terms and the same functions: the same objects, or (with `sigma`) equal f^(d)(sigma) for
     d < orders.  O(nnz) host comparison, once per call."""
-    if not (isinstance(nep, AbstractSPMF) and isinstance(nept, AbstractSPMF)):
+    if not (pure_spmf(nep, "Mlincomb") and pure_spmf(nept, "Mlincomb")):
         return None
-    for x in (nep, nept):
-        if type(x).compute_Mlincomb is not AbstractSPMF.compute_Mlincomb:
-            return None
     Av, At = nep.get_Av(), nept.get_Av()
     if len(Av) != len(At) or not _same_functions(nep.get_fv(), nept.get_fv(), sigma, orders):
         return None

@@ -777,6 +777,49 @@ def test_beyn_first_call_seeds_the_device_plan(na, monkeypatch):
             _match(l1, ref, 1e-8)
 
 
+def test_beyn_nep_with_part_outside_its_terms_takes_the_host_route(na, monkeypatch):
+    """a NEP whose compute_Mder adds a matrix outside its SPMF terms (here 1e-3 mean|diag A_1| lam I, on entries of the union
+    pattern) must not be factorised from the terms alone, although the pattern of its terms has a ready plan: no plan is used by
+    the call, and the eigenvalues are those of the all-host run (1e-8, as in the tests around this one).  Before the terms
+    route asked for an unmodified compute_Mder the call factorised all N nodes on the plan of the terms, without the extra part
+    (plan uses 15 -> 31), and returned the eigenvalues of the plain NEP: 4.5e-4 relative away from the all-host run, 4.5e4 times
+    the tolerance (4.5e-6 with a part of 1e-5 mean|diag A_1|).  With the gate the difference is 1.6e-12."""
+    import scipy.sparse as sp
+    from nep_amd.linsolvers import _DeviceRefactor
+    n, k, N = 1310, 16, 16
+    nep = na.nep_gallery("gun_spmf", n)
+    shift = 1e-3 * float(np.abs(nep.get_Av()[1].diagonal()).mean())
+
+    class WithDiagonalPart(type(nep)):
+        def compute_Mder(self, lam, i=0):
+            A = sp.csc_matrix(super().compute_Mder(lam, i))
+            cols = np.repeat(np.arange(A.shape[1]), np.diff(A.indptr))
+            diag = np.nonzero(A.indices == cols)[0]
+            assert len(diag) == A.shape[0]                         # the whole diagonal is in the pattern
+            data = A.data.astype(np.complex128)
+            data[diag] += shift * (lam if i == 0 else float(i == 1))
+            return sp.csc_matrix((data, A.indices, A.indptr), shape=A.shape)
+
+    sub = na.nep_gallery("gun_spmf", n)
+    sub.__class__ = WithDiagonalPart
+    Vh = na.probe_block(n, k)
+    kw = dict(sigma=250.0 ** 2, radius=1.2e4, N=N, k=k, neigs=10 ** 6, tol=1e-6, sanity_check=False)
+    _DeviceRefactor.clear()
+    na.contour_beyn(nep, Vh=Vh, **kw)                              # seeds the plan of the terms' pattern
+    _DeviceRefactor.wait()
+    counts = {key: p["uses"] + p["fails"] for key, p in _DeviceRefactor.plans.items()}
+    assert any(p["state"] == "ready" for p in _DeviceRefactor.plans.values()) == _DeviceRefactor.enabled()
+    lam, _ = na.contour_beyn(sub, Vh=Vh, **kw)
+    _DeviceRefactor.wait()
+    assert all(_DeviceRefactor.plans[key]["uses"] + _DeviceRefactor.plans[key]["fails"] == c for key, c in counts.items())
+    monkeypatch.setenv("NEP_BEYN_HOST_LU", "1")
+    lam_host, _ = na.contour_beyn(sub, Vh=Vh, **kw)
+    print("largest eigenvalue difference to the all-host run: %.3e (relative to max(1, |lam|))"
+          % max(min(abs(x - y) for y in lam_host) / max(1.0, abs(x)) for x in lam))
+    assert len(lam) == len(lam_host) >= 1
+    _match(lam, lam_host, 1e-8)
+
+
 def test_block_SS_dep0_kat_and_gun_twin(na):
     """test/contour_block_SS.jl:9-24 on the device path (three variants), then a sparse gun twin against the oracle with
     the same probe blocks: same numerical rank, eigenvalues inside the contour agree to 1e-7 relative."""
