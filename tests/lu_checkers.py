@@ -7,7 +7,8 @@ against the block maximum, level count, chunk boundaries and the stored diagonal
 `check(impl, case)` runs `impl(recipe, ops)` and compares every result buffer with the reference.  `impl` receives the factor
 arrays of the case (`Recipe`) and a list of solve calls (`Op`) with flat complex128 buffers in place of device pointers and returns
 the X buffer of every call; test_gpu_lu_checkers.py passes an adapter that builds ONE handle per recipe and runs all calls on it,
-test_host_lu_checkers.py passes `ref_impl` (float64) and its mutants.
+test_host_lu_checkers.py passes `ref_impl` (float64) and its mutants.  The last section holds the same for the device numeric
+factorisation (csrc/lufac.hip): closed fill patterns, the plan's classification restated, `ref_refactor` and its mutants.
 
 Two kinds of case (as in primitive_checkers.py):
   exact    L unit lower with off-diagonal entries in {0, +-1, +-i}, diag(U) in {+-1, +-i}, X Gaussian integers, B = A X formed in
@@ -21,14 +22,16 @@ Two kinds of case (as in primitive_checkers.py):
   rounded  random complex factors with dominant diagonal, reference in np.clongdouble, assertion
            |impl - ref| <= |scale| (C_BLOCK cbound(N, W) + cbound(1, |x| + |add|)),  W = M(U)^-1 (|U||x| + M(L)^-1 |L||y|).
 """
-from functools import partial
+from bisect import bisect_right
+from functools import lru_cache, partial
 
 import numpy as np
 import scipy.sparse as sp
 from scipy.sparse.linalg import spsolve_triangular
 
 from primitive_checkers import (Case, assert_exact, assert_bounded, assert_below_2_53, cbound, colmajor_buf, cm_view, gint, grand,
-                                perturb, RATIOS, SENT, NAN, C128, CLD, _seed)
+                                perturb, RATIOS, SENT, NAN, C128, CLD, SQ2, _seed)
+from primitive_checkers import U as UNIT_ROUNDOFF
 
 ML_BMAX = 256                 # largest diagonal block of csrc/trsv_ml.hip
 NRHS = [1, 2, 3, 4, 5, 7, 8, 9, 13, 32, 33]
@@ -678,3 +681,594 @@ def check(impl, c, name="nep_lu_solve", args=None, cache=None):
         else:
             assert_bounded("%s %s" % (name, c.group.split("/")[0]), c, np.asarray(g)[blk], wnt, bound)
     return len(ops)
+
+
+# ================================================================================================================================
+# the device numeric factorisation (csrc/lufac.hip: nep_lu_refac_create / nep_lu_factor_dev[_batch[_terms]]): patterns closed under
+# fill, the plan's classification of the products restated, a right-looking reference in step and in panel order, its mutants
+#
+# Exact cases: units on a closed pattern (one entry in ten an explicit zero, never the parent edge), A = L U on integers.  Every
+# partial sum of any elimination order is A_ij minus a subset of the products L_ik U_kj, a Gaussian integer bounded by
+# 2 (|L||U|)_ij (asserted < 2^53 per case); a division by a unit pivot is exact.  The device factor therefore equals the generated
+# one bit for bit, step by step or in panels.  Rounded cases: the diagonally dominant scaling of make_recipe, assertion
+#     |A - L^ U^|_ij <= C_REFAC cbound(N_ij + 1, (|L^||U^|)_ij),   N_ij = stored products of the entry (+ 1: its closing term),
+# evaluated in np.clongdouble.
+#
+# C_REFAC: cbound(N + 1, .) is already the bound of a sum of N + 1 rounded products subtracted from a_ij in any order; the panel
+# form needs a margin over it because its multiplier F(i,k) / pivot is recomputed per product (and the in-panel eliminations are
+# repeated per destination) and may differ in the last bit from the stored L^ the residual is formed with.  Measured on the host
+# (test_host_lu_checkers.py::test_refactor_emulation_sets_the_constant): float64 ref_refactor in step order and in panel order
+# P = 2, 3, 4 over every rounded case gives
+#     r = max |A - L^ U^| / cbound(N + 1, |L^||U^|) = 0.2963       (largest at arrow/m300_t41/unsym, nep_lu_factor_dev, step order)
+# and c is the smallest power of two >= 4 r (the factor 4 as for C_BLOCK: other summation order -- 4 / 16 lanes per external
+# segment --, fused multiply-adds, the device's division).
+R_REFAC_MEASURED = 0.2963
+C_REFAC = 2.0
+
+
+def close_pattern(n, Lrows, Lcols, Urows=None, Ucols=None):
+    """symbolic right-looking fill: pivot k adds (i, j) for every i in L(:,k), j in U(k,:) -- to L where i > j, to U where i < j.
+    Returns (Lrows, Lcols) of the strict pattern of L by columns and (Urows, Ucols) of the strict pattern of U by rows; U
+    defaults to the transposed pattern of L"""
+    if Urows is None:
+        Urows, Ucols = Lcols, Lrows
+    Lc = [set() for _ in range(n)]; Ur = [set() for _ in range(n)]
+    for i, j in zip(np.asarray(Lrows).tolist(), np.asarray(Lcols).tolist()):
+        assert i > j
+        Lc[j].add(i)
+    for i, j in zip(np.asarray(Urows).tolist(), np.asarray(Ucols).tolist()):
+        assert i < j
+        Ur[i].add(j)
+    for k in range(n):
+        if not Lc[k] or not Ur[k]:
+            continue
+        ls, us = sorted(Lc[k]), sorted(Ur[k])
+        for j in us:
+            Lc[j].update(ls[bisect_right(ls, j):])
+        for i in ls:
+            Ur[i].update(us[bisect_right(us, i):])
+    lr = np.array([i for k in range(n) for i in sorted(Lc[k])], dtype=np.int64)
+    lc_ = np.repeat(np.arange(n, dtype=np.int64), [len(s) for s in Lc])
+    uc = np.array([j for k in range(n) for j in sorted(Ur[k])], dtype=np.int64)
+    ur = np.repeat(np.arange(n, dtype=np.int64), [len(s) for s in Ur])
+    return lr, lc_, ur, uc
+
+
+def fam_grid(nx, ny, rng):
+    """five-point grid in natural order (node = x + nx y): closed, it is the full band of width nx; its elimination tree is a chain"""
+    node = np.arange(nx * ny, dtype=np.int64)
+    x = node % nx
+    east = node[x < nx - 1]; north = node[node < nx * (ny - 1)]
+    return nx * ny, np.r_[east + 1, north + nx], np.r_[east, north]
+
+
+# name: (generator of the pattern that is closed, U != L^T before closing, forced block maximum or None).  Wide levels (<= 16
+# blocks, level >= 1) and their pivot counts at the block maximum 256: arrow 41 (1 mod 4), two_tier 30 (2 mod 4), bin11 7 (3 mod 4),
+# the grids 256 + 64 and 256 + 8 (0 mod 4; banded tops).  bin11 at block maximum 8: levels of 256 / 32 / 4 / 1 blocks of 7, 7, 7, 3
+# pivots -- level 1 is NOT wide and runs k_lu_int on external input.
+REFAC_CLOSED = {
+    "arrow/m300_t41": (partial(fam_arrow, 300, 41), False, None),
+    "arrow/m300_t41/unsym": (partial(fam_arrow, 300, 41), True, None),
+    "two_tier/m1500_t30": (partial(fam_two_tier, 1500, 30), False, None),
+    "two_tier/m1500_t30/unsym": (partial(fam_two_tier, 1500, 30), True, None),
+    "tree/bin11_p0.3": (partial(fam_tree, 11, 2, 0.3), False, None),
+    "tree/bin11_p0.3/unsym": (partial(fam_tree, 11, 2, 0.3), True, None),
+    "tree/bin11_p0.3/bmax8": (partial(fam_tree, 11, 2, 0.3), False, 8),
+    "grid/24x24": (partial(fam_grid, 24, 24), False, None),
+    "grid/13x40": (partial(fam_grid, 13, 40), False, None),
+}
+REFAC_NOT_CLOSED = ("arrow/m1500_t64", "two_tier/m3000_t32", "tree/bin11_p0.3")      # of FAMILIES: refused by the plan builder
+LU_WIDE_MAXBLK = 16                       # csrc/lufac.hip: a level >= 1 with at most 16 blocks is wide
+LU_WIDE_PS = (1, 2, 3, 4)                 # NEP_LU_WIDE_P
+
+
+@lru_cache(maxsize=None)
+def closed_pattern(fam):
+    """(n, Lrows, Lcols, Urows, Ucols) of the family: the closure of its generator's pattern; the unsymmetric variant keeps in U only
+    the parent edge of every column and a random half of the other entries before closing"""
+    gen, unsym, _ = REFAC_CLOSED[fam]
+    base = fam[:-len("/unsym")] if unsym else fam
+    n, rows, cols = gen(np.random.default_rng(_seed("pattern" + base.replace("/bmax8", ""))))
+    o = np.lexsort((rows, cols)); rows, cols = rows[o], cols[o]
+    if unsym:
+        rng = np.random.default_rng(_seed("unsym" + fam))
+        keep = np.r_[True, cols[1:] != cols[:-1]] | (rng.random(len(rows)) < 0.5)
+        return (n,) + close_pattern(n, rows, cols, cols[keep], rows[keep])
+    return (n,) + close_pattern(n, rows, cols)
+
+
+def make_closed_recipe(fam, kind, vset=0):
+    """factor arrays (CSC, diagonal of L stored, random permutations) with values of `kind` on the closed pattern of the family;
+    `vset` numbers independent value sets of the same pattern, layout and permutations (exact sets after the first: U times 4)"""
+    n, lr, lc_, ur, uc = closed_pattern(fam)
+    rng = np.random.default_rng(_seed("closed%s%s%d" % (fam, kind, vset)))
+    lv, _ = _values(kind, rng, lr, lc_, n, False)
+    uv, ud = _values(kind, rng, uc, ur, n, True)             # (rows of U play the part of the columns of L: first entry = parent edge)
+    if kind == "exact" and vset:                                  # max |U| != max |L|; a division by 4 u, u a unit, is as exact
+        uv, ud = 4 * uv, 4 * ud
+    if kind == "rounded":
+        if len(lr):
+            lv = lv * 0.35 / np.bincount(lr, minlength=n)[lr]
+        if len(ur):
+            uv = uv * 0.35 * np.abs(ud[ur]) / np.bincount(ur, minlength=n)[ur]
+    di = np.arange(n)
+    L = sp.coo_matrix((np.r_[lv, np.ones(n, dtype=C128)], (np.r_[lr, di], np.r_[lc_, di])), shape=(n, n)).tocsc()
+    U = sp.coo_matrix((np.r_[uv, ud], (np.r_[ur, di], np.r_[uc, di])), shape=(n, n)).tocsc()
+    L.sort_indices(); U.sort_indices()
+    erng = np.random.default_rng(_seed("emit" + fam))
+    rec = Recipe(n, 1, L.indptr.astype(np.int32), L.indices.astype(np.int32), L.data.astype(C128), U.indptr.astype(np.int32),
+                 U.indices.astype(np.int32), U.data.astype(C128), erng.permutation(n).astype(np.int32), erng.permutation(n).astype(np.int32),
+                 kind=kind)
+    assert len(rec.Lx) == len(lr) + n and len(rec.Ux) == len(ur) + n      # (explicit zeros are kept)
+    rec.fam = fam
+    rec.bmax = REFAC_CLOSED[fam][2]
+    return rec
+
+
+def matrix_of(rec):
+    """A in the caller's numbering with Pr A Pc = L U, formed on integers: A[i, j] = (L U)[perm_r[i], perm_c[j]]; its CSC pattern is
+    the structural product (entries that cancel stay, as explicit zeros)"""
+    n = rec.n
+    L, U = rec.matrices(C128)
+    Lp_, Up_ = rec.matrices(pattern=True)
+    P = (Lp_ @ Up_).tocsc(); P.sort_indices()
+    V = (L @ U).tocsc()
+    pr, pc = np.asarray(rec.perm_r), np.asarray(rec.perm_c)
+    ipr = np.empty(n, int); ipr[pr] = np.arange(n); ipc = np.empty(n, int); ipc[pc] = np.arange(n)
+    Pc = P.tocoo()
+    A = sp.csc_matrix((np.ones(Pc.nnz), (ipr[Pc.row], ipc[Pc.col])), shape=(n, n)); A.sort_indices()
+    Ac = A.tocoo()
+    vals = np.asarray(V[pr[Ac.row], pc[Ac.col]]).reshape(-1).astype(C128)
+    A = sp.csc_matrix((vals + 0, (Ac.row, Ac.col)), shape=(n, n))
+    # (csc_matrix from COO drops nothing: explicit zeros are kept)
+    A.sort_indices()
+    return A
+
+
+def one_norm(z):
+    return np.abs(z.real) + np.abs(z.imag)
+
+
+class Products:
+    """every update F(i,j) -= L(i,k) U(k,j) of the factorisation of a pattern, classified as refac_build of csrc/lufac.hip does.
+    Positions are those of the device array F: entry e of the given L at e, entry e of the given U at nnz(L) + e.
+
+    k, i, j, gL, gU, gd   per product, pivots ascending, within a pivot by (column j, row i)
+    kind                  0 internal (destination pivot min(i,j) in the block of k, level not wide), 2 wide (the same on a wide level),
+                          1 external (destination pivot in a block of a higher level)
+    dlev, seg             level of the destination pivot; segment of an external product (-1 otherwise)
+    ext                   the external products ordered by (dlev, gd, k); ext_seg / ext_dst: first product / destination of every
+                          segment (one per destination), ext_lev[l]: segment range of level l, lanes[l]: lane count k_lu_ext runs with
+    counts                [products, internal, external, segments, wide, wide steps, levels] as nep_lu_refac_analyze reports them"""
+
+    def __init__(self, rec, bmax=None):
+        n = self.n = rec.n
+        Lp, Li, Up, Ui = (np.asarray(a, dtype=np.int64) for a in (rec.Lp, rec.Li, rec.Up, rec.Ui))
+        nnzL, nnzU = len(Li), len(Ui)
+        self.nnzL, self.nnzU, self.nF = nnzL, nnzU, nnzL + nnzU
+        lcol = np.repeat(np.arange(n), np.diff(Lp)); ucol = np.repeat(np.arange(n), np.diff(Up))
+        assert np.all(Li >= lcol) and np.all(Ui <= ucol)
+        self.ldiag = np.flatnonzero(Li == lcol); self.udiag = nnzL + np.flatnonzero(Ui == ucol)
+        assert len(self.ldiag) == n and len(self.udiag) == n
+        ls = np.flatnonzero(Li > lcol)
+        ls = ls[np.lexsort((Li[ls], lcol[ls]))]                      # strict L by (column, row)
+        us = np.flatnonzero(Ui < ucol)
+        us = us[np.lexsort((ucol[us], Ui[us]))]                      # strict U by (row, column)
+        self.Lrow, self.Lcol, self.Lpos = Li[ls], lcol[ls], ls
+        self.Urow, self.Ucol, self.Upos = Ui[us], ucol[us], nnzL + us
+        self.Lptr = np.r_[0, np.cumsum(np.bincount(self.Lcol, minlength=n))]
+        self.Uptr = np.r_[0, np.cumsum(np.bincount(self.Urow, minlength=n))]
+        # (i, j) -> position: the strict entries and the diagonal of U
+        keys = np.r_[self.Lrow * n + self.Lcol, self.Urow * n + self.Ucol, np.arange(n) * (n + 1)]
+        poss = np.r_[self.Lpos, self.Upos, self.udiag]
+        o = np.argsort(keys)
+        self._keys, self._poss = keys[o], poss[o]
+        # products
+        nl, nu = np.diff(self.Lptr), np.diff(self.Uptr)
+        cnt = nl * nu
+        pbase = np.r_[0, np.cumsum(cnt)]
+        k = np.repeat(np.arange(n), cnt)
+        local = np.arange(pbase[-1]) - pbase[k]
+        a, b = local // np.maximum(nl[k], 1), local % np.maximum(nl[k], 1)
+        ue, le = self.Uptr[k] + a, self.Lptr[k] + b
+        self.k, self.i, self.j, self.gL, self.gU = k, self.Lrow[le], self.Ucol[ue], self.Lpos[le], self.Upos[ue]
+        self.gd = self.pos(self.i, self.j)
+        self.closed = bool(np.all(self.gd >= 0))
+        if not self.closed:                                         # (an update without a slot: nothing further is defined)
+            return
+        # partition and classes
+        Lpat, Upat = rec.matrices(pattern=True)
+        _, lvl, bid = reference_partition(n, Lpat, Upat, bmax or getattr(rec, "bmax", None) or ML_BMAX)
+        self.lvl, self.bid = lvl, bid
+        nlev = self.nlev = int(lvl.max()) + 1
+        self.blocks = [[np.flatnonzero(bid == r) for r in np.unique(bid[lvl == l])] for l in range(nlev)]     # by root index; pivots ascending
+        self.wide = np.array([l >= 1 and len(self.blocks[l]) <= LU_WIDE_MAXBLK for l in range(nlev)])
+        self.steps = int(sum(max(len(b) for b in self.blocks[l]) for l in range(nlev) if self.wide[l]))
+        p = np.minimum(self.i, self.j)
+        same = bid[p] == bid[k]
+        assert np.all(same | (lvl[p] > lvl[k])), "an update crosses blocks of one level"
+        self.kind = np.where(same, np.where(self.wide[lvl[k]], 2, 0), 1)
+        self.dlev = lvl[p]
+        self.pptr = pbase                                           # products of pivot k: pptr[k] : pptr[k + 1]
+        e = np.flatnonzero(self.kind == 1)
+        self.ext = e[np.lexsort((self.k[e], self.gd[e], self.dlev[e]))]
+        ge, de = self.gd[self.ext], self.dlev[self.ext]
+        first = np.r_[True, ge[1:] != ge[:-1]] if len(ge) else np.zeros(0, bool)
+        self.ext_seg = np.r_[np.flatnonzero(first), len(ge)]
+        self.ext_dst = ge[first]
+        seglev = de[first]
+        self.ext_lev = [np.searchsorted(seglev, [l, l + 1]) for l in range(nlev)]
+        self.seg = np.full(len(k), -1)
+        self.seg[self.ext] = np.cumsum(first) - 1
+        self.lanes = []
+        for l in range(nlev):
+            s0, s1 = self.ext_lev[l]
+            avg = self.mean_segment_length(l)
+            self.lanes.append(0 if s1 == s0 else 16 if avg > 48.0 else 4 if avg > 6.0 else 1)
+        self.counts = [len(k), int(np.sum(self.kind == 0)), len(self.ext), len(self.ext_dst), int(np.sum(self.kind == 2)), self.steps, nlev]
+        self._panels = {}
+        # A: the structural product in the caller's numbering -> positions (amap), as nep_lu_refac_create is given it
+        A = matrix_of(rec)
+        self.Ap, self.Ai = A.indptr.astype(np.int32), A.indices.astype(np.int32)
+        acol = np.repeat(np.arange(n), np.diff(A.indptr))
+        fi, fj = np.asarray(rec.perm_r, dtype=np.int64)[A.indices], np.asarray(rec.perm_c, dtype=np.int64)[acol]
+        self.amap = self.pos(fi, fj)
+        assert np.all(self.amap >= 0)
+        self.by_dst = np.argsort(self.gd, kind="stable")
+        gs = self.gd[self.by_dst]
+        self.dst_first = np.flatnonzero(np.r_[True, gs[1:] != gs[:-1]]) if len(gs) else np.zeros(0, int)
+        self.dst_pos = gs[self.dst_first]
+
+    def pos(self, i, j):
+        """position of F(i, j), -1 where the entry is not stored"""
+        key = np.asarray(i, dtype=np.int64) * self.n + np.asarray(j, dtype=np.int64)
+        q = np.minimum(np.searchsorted(self._keys, key), len(self._keys) - 1)
+        return np.where(self._keys[q] == key, self._poss[q], -1)
+
+    def mean_segment_length(self, l):
+        """external products per destination of level l: what lu_factor_batch_impl picks the lane count of k_lu_ext from"""
+        s0, s1 = self.ext_lev[l]
+        return (self.ext_seg[s1] - self.ext_seg[s0]) / (s1 - s0) if s1 > s0 else 0.0
+
+    def pivot_products(self, k, kind):
+        t = np.arange(self.pptr[k], self.pptr[k + 1])
+        return t[self.kind[t] == kind]
+
+    def panels(self, P):
+        """the panel form of the wide levels (refac_build_fused) for panels of P pivots: per wide level the panels
+        (pivots, hdr = positions of their P x P diagonal block, dst, lr, ur = record operands P x records, own = the pivot has a
+        product of its own for the record) and the deferred products of every round (gL, gU, gd, position of the pivot)"""
+        if P in self._panels:
+            return self._panels[P]
+        out = {}
+        nrec = nfix = launches = nsteps = 0
+        for l in range(self.nlev):
+            if not self.wide[l]:
+                continue
+            pans, defer, step_rec = [], [[] for _ in range(P - 1)], {}
+            for blk in self.blocks[l]:
+                for s, q0 in enumerate(range(0, len(blk), P)):
+                    ks = blk[q0:q0 + P]
+                    hdr = np.full((P, P), -1, dtype=np.int64)
+                    hdr[:len(ks), :len(ks)] = self.pos(ks[:, None], ks[None, :])
+                    rest = []
+                    for r, kk in enumerate(ks):
+                        t = self.pivot_products(kk, 2)
+                        later = ks[r + 1:]
+                        d = np.isin(self.i[t], later) | np.isin(self.j[t], later)
+                        if d.any():
+                            defer[r].append(t[d])
+                        rest.append(t[~d])
+                    rest = np.concatenate(rest) if rest else np.zeros(0, int)
+                    dst, ix = np.unique(self.gd[rest], return_index=True)
+                    di, dj = self.i[rest][ix], self.j[rest][ix]
+                    lr = np.full((P, len(dst)), -1, dtype=np.int64); ur = lr.copy()
+                    lr[:len(ks)] = self.pos(di[None, :], ks[:, None]); ur[:len(ks)] = self.pos(ks[:, None], dj[None, :])
+                    pans.append(dict(ks=ks, hdr=hdr, dst=dst, lr=lr, ur=ur, own=(lr >= 0) & (ur >= 0)))
+                    step_rec[s] = step_rec.get(s, 0) + len(dst)
+                    nrec += len(dst)
+            defer = [np.concatenate(d) if d else np.zeros(0, int) for d in defer]
+            for t in defer:
+                assert len(np.unique(self.gd[t])) == len(t)           # one launch, one product per destination
+            nfix += sum(len(t) for t in defer)
+            launches += sum(c > 0 for c in step_rec.values()) + sum(len(t) > 0 for t in defer)
+            nsteps += len(step_rec)
+            out[l] = (pans, defer)
+        self._panels[P] = out
+        out["info"] = dict(records=nrec, deferred=nfix, launches=launches, panel_steps=nsteps, wide_levels=int(self.wide.sum()))
+        return out
+
+
+@lru_cache(maxsize=None)
+def classify_products(fam_or_rec, bmax=None):
+    """the plan's classification (Products) of a closed family, or of a recipe; `bmax`: block maximum of the partition (default: the
+    family's forced one, or 256)"""
+    rec = make_closed_recipe(fam_or_rec, "exact") if isinstance(fam_or_rec, str) else fam_or_rec
+    return Products(rec, bmax)
+
+
+REFAC_MUTANTS = ("deferred_dropped", "chain_operand_missing", "short_panel_as_full", "ext_tail_dropped", "last_wide_column_unscaled",
+                 "batch_reads_first_matrix", "terms_first_coefficients", "growth_from_L", "breakdown_unreported", "perturb")
+
+
+def ref_refactor(rec, Ax_or_terms, P=1, mut=None, dt=C128, plan=None):
+    """right-looking elimination of A on the stored pattern with the stored pivot order, in dtype dt, level by level as
+    lu_factor_batch_impl: the external products of a level summed per destination, then its pivots -- one by one (block levels;
+    wide levels at P = 1, the column of L divided at the end of the level) or in panels of P (wide levels, P >= 2: one
+    destination's P products summed first from a bordered elimination of its own, the products into the panel's own later rows and
+    columns deferred to P - 1 rounds at the end of the level).
+
+    Ax_or_terms: the values of A in the CSC order of matrix_of(rec) (nnz, or B x nnz for a batch), or a pair (D, Cf) of term values
+    (nnz x mt) and coefficients (mt, or B x mt).  Returns (Lx, Ux, health) -- with a leading batch axis where the input had one --,
+    health = [broken pivot, max (|Re| + |Im|) over L, max |U| / max |A| in the same norm].  `mut` names a defect (REFAC_MUTANTS)"""
+    pl = plan if plan is not None else Products(rec)
+    if isinstance(Ax_or_terms, tuple):
+        D, Cf = Ax_or_terms
+        single = np.ndim(Cf) == 1
+        Cf = np.atleast_2d(Cf)
+        if mut == "terms_first_coefficients":
+            Cf = np.repeat(Cf[:1], len(Cf), axis=0)
+        A = np.zeros((len(Cf), D.shape[0]), dtype=dt)
+        for t in range(D.shape[1]):
+            A += Cf[:, t].astype(dt)[:, None] * D[:, t].astype(dt)[None, :]
+    else:
+        single = np.ndim(Ax_or_terms) == 1
+        A = np.atleast_2d(Ax_or_terms).astype(dt)
+    B = len(A)
+    F = np.zeros((B, pl.nF), dtype=dt)
+    F[:, pl.amap] = A
+    F[:, pl.ldiag] = 1
+    broken = np.zeros(B, bool)
+    gL, gU, gd, ud = pl.gL, pl.gU, pl.gd, pl.udiag
+    lmax = np.zeros(B)
+
+    def scale_column(k):
+        piv = F[:, ud[k]]
+        ap = one_norm(piv).astype(np.float64)
+        broken[:] |= ~(ap > 0.0) | ~np.isfinite(ap)
+        e = pl.Lpos[pl.Lptr[k]:pl.Lptr[k + 1]]
+        if len(e):
+            F[:, e] = F[:, e] / piv[:, None]
+
+    with np.errstate(all="ignore"):
+        for l in range(pl.nlev):
+            s0, s1 = pl.ext_lev[l]
+            if s1 > s0:
+                t = pl.ext[pl.ext_seg[s0]:pl.ext_seg[s1]]
+                prod = F[:, gL[t]] * F[:, gU[t]]
+                starts = pl.ext_seg[s0:s1] - pl.ext_seg[s0]
+                if mut == "ext_tail_dropped" and pl.lanes[l] > 1:
+                    lens = np.diff(pl.ext_seg[s0:s1 + 1])
+                    within = np.arange(len(t)) - np.repeat(starts, lens)
+                    prod[:, within >= np.repeat(lens // pl.lanes[l] * pl.lanes[l], lens)] = 0
+                F[:, pl.ext_dst[s0:s1]] -= np.add.reduceat(prod, starts, axis=1)
+            pivots = np.sort(np.concatenate(pl.blocks[l]))
+            if not pl.wide[l]:
+                for k in pivots:
+                    scale_column(k)
+                    t = pl.pivot_products(k, 0)
+                    if len(t):
+                        F[:, gd[t]] -= F[:, gL[t]] * F[:, gU[t]]
+                continue
+            if P == 1:
+                for k in pivots:
+                    t = pl.pivot_products(k, 2)
+                    if len(t):
+                        F[:, gd[t]] -= (F[:, gL[t]] / F[:, ud[k]][:, None]) * F[:, gU[t]]
+            else:
+                pans, defer = pl.panels(P)[l]
+                # (short_panel_as_full: a short last panel never has records -- every later pivot of its block lies inside it, so all its
+                # products are deferred -- and the np < P branch of k_lu_widep cannot show in a result; the form of the defect that can is
+                # a plan that counts only full panels, steps / P, and so loses the short panel's products)
+                short = [pn["ks"] for pn in pans if len(pn["ks"]) < P] if mut == "short_panel_as_full" else []
+                short = np.concatenate(short) if short else np.zeros(0, int)
+                for pn in pans:
+                    npv = len(pn["ks"])
+                    if not len(pn["dst"]) or (mut == "short_panel_as_full" and npv < P):
+                        continue
+                    Fd = F[:1] if mut == "batch_reads_first_matrix" else F
+                    Dv = np.where(pn["hdr"] >= 0, Fd[:, np.maximum(pn["hdr"], 0)], 0) + np.zeros((B, 1, 1), dtype=dt)
+                    lr, ur = pn["lr"], pn["ur"]
+                    if mut == "chain_operand_missing":
+                        lr, ur = np.where(pn["own"], lr, -1), np.where(pn["own"], ur, -1)
+                    LR = np.where(lr >= 0, F[:, np.maximum(lr, 0)], 0)            # B x P x records
+                    UR = np.where(ur >= 0, F[:, np.maximum(ur, 0)], 0)
+                    acc = np.zeros((B, len(pn["dst"])), dtype=dt)
+                    for q in range(npv):
+                        pv = Dv[:, q, q]
+                        for r2 in range(q + 1, P):
+                            m = Dv[:, r2, q] / pv
+                            Dv[:, r2, q + 1:] -= m[:, None] * Dv[:, q, q + 1:]
+                            UR[:, r2] -= m[:, None] * UR[:, q]
+                        ml = LR[:, q] / pv[:, None]
+                        for c in range(q + 1, P):
+                            LR[:, c] -= ml * Dv[:, q, c][:, None]
+                        acc += ml * UR[:, q]
+                    F[:, pn["dst"]] -= acc
+                if mut != "deferred_dropped":
+                    for r, t in enumerate(defer):
+                        t = t[~np.isin(pl.k[t], short)]
+                        if len(t):
+                            F[:, gd[t]] -= (F[:, gL[t]] / F[:, ud[pl.k[t]]]) * F[:, gU[t]]
+            for k in (pivots[:-1] if mut == "last_wide_column_unscaled" else pivots):
+                scale_column(k)
+        Lx, Ux = F[:, :pl.nnzL], F[:, pl.nnzL:]
+        health = np.zeros((B, 3))
+        amax = one_norm(A).astype(np.float64).max(axis=1) if A.shape[1] else np.zeros(B)
+        lmax = one_norm(F[:, pl.Lpos]).astype(np.float64).max(axis=1) if len(pl.Lpos) else np.zeros(B)
+        uabs = one_norm(Ux).astype(np.float64)
+        umax = np.where(np.isnan(uabs).any(axis=1), 1.0e300, np.nan_to_num(uabs, nan=0.0).max(axis=1))
+        health[:, 0] = 0.0 if mut == "breakdown_unreported" else broken
+        health[:, 1] = lmax
+        top = lmax if mut == "growth_from_L" else umax
+        health[:, 2] = np.where(amax > 0.0, top / np.where(amax > 0.0, amax, 1.0), np.where(top > 0.0, 1.0e300, 0.0))
+    if mut == "perturb":
+        Ux = Ux.copy(); Ux[-1] = perturb(Ux[-1])
+    return (Lx[0], Ux[0], health[0]) if single else (Lx, Ux, health)
+
+
+def factor_residual(pl, Ax, Lx, Ux):
+    """(|A - L U| per stored position, (|L||U|) there, number of stored products there) for factor values in the entry order of the
+    recipe, the products summed in np.clongdouble; the unit diagonal of L is taken as exact"""
+    Fv = np.r_[Lx, Ux].astype(CLD)
+    Fv[pl.ldiag] = 1
+    Fa = np.abs(Fv).astype(np.float64)
+    S = np.zeros(pl.nF, dtype=CLD); Sa = np.zeros(pl.nF); N = np.zeros(pl.nF, dtype=np.int64)
+    if len(pl.gd):
+        o = pl.by_dst
+        S[pl.dst_pos] = np.add.reduceat(Fv[pl.gL[o]] * Fv[pl.gU[o]], pl.dst_first)
+        Sa[pl.dst_pos] = np.add.reduceat(Fa[pl.gL[o]] * Fa[pl.gU[o]], pl.dst_first)
+        N[pl.dst_pos] = np.diff(np.r_[pl.dst_first, len(o)])
+    # closing term: L(i,j) U(j,j) below the diagonal, 1 U(i,j) on and above it
+    S[pl.Lpos] += Fv[pl.Lpos] * Fv[pl.udiag[pl.Lcol]]; Sa[pl.Lpos] += Fa[pl.Lpos] * Fa[pl.udiag[pl.Lcol]]
+    up = np.r_[pl.Upos, pl.udiag]
+    S[up] += Fv[up]; Sa[up] += Fa[up]
+    Af = np.zeros(pl.nF, dtype=CLD); Af[pl.amap] = np.asarray(Ax).astype(CLD)
+    keep = np.ones(pl.nF, bool); keep[pl.ldiag] = False
+    return np.abs(Af - S).astype(np.float64)[keep], Sa[keep], N[keep]
+
+
+def refac_ratio(pl, Ax, Lx, Ux):
+    """largest |A - L U|_ij / cbound(N_ij + 1, (|L||U|)_ij); infinite for a non-finite factor"""
+    if not (np.all(np.isfinite(Lx)) and np.all(np.isfinite(Ux))):
+        return np.inf
+    res, Sa, N = factor_residual(pl, Ax, Lx, Ux)
+    g = (2.0 * (N + 1) + 6.0) * UNIT_ROUNDOFF                    # cbound(N + 1, S) with N an array
+    return float(np.max(res / np.maximum(SQ2 * g / (1.0 - g) * Sa, np.finfo(np.float64).tiny)))
+
+
+def assert_refac_bounded(name, c, pl, Ax, Lx, Ux, c_refac=None):
+    ratio = refac_ratio(pl, Ax, Lx, Ux) / (C_REFAC if c_refac is None else c_refac)
+    RATIOS[name] = max(RATIOS.get(name, 0.0), ratio)
+    assert ratio <= 1.0, "%s %r: |A - L U| / bound = %.3g" % (name, c, ratio)
+    return ratio
+
+
+@lru_cache(maxsize=None)
+def refac_inputs(fam, kind):
+    """what one closed family's tests share: the recipe, a second value set of its pattern, A and its values for both, the plan's
+    classification, and (exact) the assertion that every partial sum of any elimination order is exact"""
+    rec, rec2 = make_closed_recipe(fam, kind, 0), make_closed_recipe(fam, kind, 1)
+    pl = classify_products(fam)
+    assert pl.closed
+    A, A2 = matrix_of(rec), matrix_of(rec2)
+    assert np.array_equal(A.indptr, pl.Ap) and np.array_equal(A.indices, pl.Ai) and np.array_equal(A2.indices, pl.Ai)
+    if kind == "exact":
+        for r_, A_ in ((rec, A), (rec2, A2)):
+            aL, aU = r_.matrices(absval=True)
+            assert_below_2_53(2.0 * (aL @ aU).max() + one_norm(A_.data).max())
+    return dict(rec=rec, rec2=rec2, Ax=np.ascontiguousarray(A.data, dtype=C128), Ax2=np.ascontiguousarray(A2.data, dtype=C128), plan=pl)
+
+
+def with_values(rec, Lx, Ux):
+    r = Recipe(rec.n, 1, rec.Lp, rec.Li, np.ascontiguousarray(Lx, dtype=C128), rec.Up, rec.Ui, np.ascontiguousarray(Ux, dtype=C128),
+               rec.perm_r, rec.perm_c, kind=rec.kind)
+    r.fam, r.bmax = rec.fam, rec.bmax
+    return r
+
+
+REFAC_FORMS = ("nep_lu_factor_dev", "nep_lu_factor_dev_batch", "nep_lu_factor_dev_batch_terms")
+
+
+@lru_cache(maxsize=None)
+def refac_forms(fam, kind):
+    """the three calls of a family: name -> (input of ref_refactor, [(recipe with the factor the call has to return, values of A)
+    per matrix]).  The batch: the matrix, i times the matrix (L the same, U times i), a second value set of the pattern.  The terms
+    (mt = 3, term 1 all zero, coefficients that differ per matrix): exact  A = T0 + (1 + i) T2 with Gaussian-integer T2, the matrices
+    A, i A, -A;  rounded  T0 = A, T2 = the second value set with coefficients (1, ., 0), (i, ., 0), (0, ., 1) -- every product and sum
+    of the assembly is exact, so the terms call factorises the very matrices of the batch"""
+    inp = refac_inputs(fam, kind)
+    rec, rec2, Ax, Ax2 = inp["rec"], inp["rec2"], inp["Ax"], inp["Ax2"]
+    rec_i = with_values(rec, rec.Lx, 1j * rec.Ux)
+    batch = [(rec, Ax), (rec_i, 1j * Ax), (rec2, Ax2)]
+    zero = np.zeros(len(Ax), dtype=C128)
+    if kind == "exact":
+        T2 = gint(np.random.default_rng(_seed("terms" + fam)), len(Ax), -3, 3)
+        D = np.stack([Ax - (1 + 1j) * T2, zero, T2], axis=1)
+        Cf = np.array([[1, 5, 1 + 1j], [1j, -2, 1j - 1], [-1, 3j, -1 - 1j]], dtype=C128)
+        tb = [(rec, Ax), (rec_i, 1j * Ax), (with_values(rec, rec.Lx, -rec.Ux), -Ax)]
+    else:
+        D = np.stack([Ax, zero, Ax2], axis=1)
+        Cf = np.array([[1, 7, 0], [1j, -3, 0], [0, 2, 1]], dtype=C128)
+        tb = batch
+    return {"nep_lu_factor_dev": (Ax, [(rec, Ax)]),
+            "nep_lu_factor_dev_batch": (np.ascontiguousarray(np.stack([a for _, a in batch])), batch),
+            "nep_lu_factor_dev_batch_terms": ((np.ascontiguousarray(D), np.ascontiguousarray(Cf)), tb)}
+
+
+def expected_health(rec, Ax):
+    """(0, max (|Re| + |Im|) over the strict part of L, max |U| / max |A|) of the factor of the recipe"""
+    L, _ = rec.matrices()
+    Ls = sp.tril(L, -1).tocsc()                                   # (explicit zeros stay: they count as 0)
+    return np.array([0.0, one_norm(Ls.data).max() if Ls.nnz else 0.0, one_norm(rec.Ux).max() / one_norm(Ax).max()])
+
+
+def refac_check(impl, fam, kind, P, c_refac=None, forms=REFAC_FORMS):
+    """impl(name, rec, input, P) -> (Lx, Ux, health), batch axis first (Lx, Ux None where the call returns no values); every matrix
+    of every call: health[0] == 0; exact: L and U bit for bit, health == (0, max |L|, max |U| / max |A|); rounded: the residual
+    bound, and the health words equal what the returned values give.  Returns the number of matrices checked"""
+    pl = refac_inputs(fam, kind)["plan"]
+    c = Case(fam, "P=%d" % P, kind, None)
+    m = 0
+    for name in forms:
+        data, want = refac_forms(fam, kind)[name]
+        Lx, Ux, health = impl(name, want[0][0], data, P)
+        Lx, Ux, health = (None if Lx is None else np.atleast_2d(Lx)), (None if Ux is None else np.atleast_2d(Ux)), np.atleast_2d(health)
+        assert len(health) == len(want)
+        for b, (rb, Ab) in enumerate(want):
+            tag = "%s[%d]" % (name, b)
+            if kind == "exact":
+                if Lx is not None:
+                    assert_exact(tag + " L", c, Lx[b], rb.Lx)
+                    assert_exact(tag + " U", c, Ux[b], rb.Ux)
+                assert_exact(tag + " health", c, health[b], expected_health(rb, Ab))
+            else:
+                assert health[b][0] == 0.0, (tag, c, health[b])
+                if Lx is not None:
+                    assert_refac_bounded("nep_lu_factor_dev %s" % fam, c, pl, Ab, Lx[b], Ux[b], c_refac)
+                    assert_exact(tag + " health", c, health[b], expected_health(with_values(rb, Lx[b], Ux[b]), Ab))
+            m += 1
+    return m
+
+
+def breakdown_cases(fam, P):
+    """exact factors with one U_kk = 0 (A = L U is exactly singular at pivot k; every earlier quantity stays an integer), k in turn
+    inside a level-0 block, the first pivot of a panel of P, a later slot of a panel (any other pivot at P = 1), pivot n - 1; and the
+    matrix itself with one NaN at an entry (i, j), i > j, whose transposed entry is stored: the product L(i,j) U(j,i) takes it to
+    pivot i.  Yields (label, pivot, values of A)"""
+    inp = refac_inputs(fam, "exact")
+    rec, pl = inp["rec"], inp["plan"]
+    b0 = max(pl.blocks[0], key=len)
+    wl = int(np.flatnonzero(pl.wide)[0])
+    ks = max(pl.blocks[wl], key=len)
+    q_first = 12 if len(ks) > 12 else 0                           # 12: slot 0 for P = 1, 2, 3, 4;  11: the last slot for P = 2, 3, 4
+    q_later = 11 if len(ks) > 12 else 1
+    assert q_first % P == 0 and (P == 1 or q_later % P != 0) and len(ks) > max(q_first, q_later)
+    picks = [("level-0 block", int(b0[len(b0) // 2])), ("first pivot of a panel", int(ks[q_first])), ("later slot of a panel", int(ks[q_later])),
+             ("last pivot", rec.n - 1)]
+    assert pl.lvl[picks[0][1]] == 0
+    for label, k in picks:
+        Ux = rec.Ux.copy()
+        Ux[pl.udiag[k] - pl.nnzL] = 0
+        yield label, k, np.ascontiguousarray(matrix_of(with_values(rec, rec.Lx, Ux)).data, dtype=C128)
+    low = np.flatnonzero(pl.amap < pl.nnzL)                        # entries of A that land in L
+    e = low[np.isin(pl.amap[low], pl.Lpos)]
+    pos = pl.amap[e]
+    srt = np.argsort(pl.Lpos)
+    at = srt[np.searchsorted(pl.Lpos[srt], pos)]
+    ok = pl.pos(pl.Lcol[at], pl.Lrow[at]) >= 0
+    e = e[ok][len(e[ok]) // 2]
+    Ax = inp["Ax"].copy()
+    Ax[e] = complex(np.nan, 0.0)
+    yield "NaN entry", -1, Ax
+
+
+def breakdown_check(impl, fam, P):
+    """every breakdown case through the single call: health[0] == 1 (the other words and the values are not specified then)"""
+    rec = refac_inputs(fam, "exact")["rec"]
+    m = 0
+    for label, k, Ax in breakdown_cases(fam, P):
+        _, _, health = impl("nep_lu_factor_dev", rec, Ax, P)
+        assert np.atleast_2d(health)[0][0] == 1.0, "%s P=%d: %s (pivot %d) not reported: health %r" % (fam, P, label, k, health)
+        m += 1
+    return m

@@ -4,8 +4,10 @@ synthetic factors of tests/lu_checkers.py, through the raw C ABI (`nep_amd._lib.
 Every case builds one handle from generated factor arrays (nep_lu_create / nep_lu_create_csc, optionally refactored, row-scaled,
 transposed) and runs at least eight solves on it (the solve numbers around the graph capture and the apex switch included):
 exact cases (Gaussian-integer factors and solutions) must match the substitution reference bit for bit at every solve, rounded
-cases stay inside the componentwise bound of lu_checkers.check.  test_host_lu_checkers.py shows that these checkers reject
-mutants and that the families have the block structure they are named for."""
+cases stay inside the componentwise bound of lu_checkers.check.  The device numeric factorisation (csrc/lufac.hip) runs on the
+closed fill patterns of lu_checkers.REFAC_CLOSED: factors bit for bit (exact) or inside the componentwise residual bound (rounded),
+pivot breakdown, a batch with broken members, the growth limit.  test_host_lu_checkers.py shows that these checkers reject mutants
+and that the families have the block structure and the product classes they are named for."""
 import ctypes as C
 import os
 import subprocess
@@ -294,27 +296,6 @@ def test_lu_apex_build_forms_in_a_child_process(na, spec):
 REFAC_FAMS = ["chain/n2", "chain/n257", "chain/n3000", "tree/20ary3_full", "dense/n63", "dense/n65", "dense/n257"]
 
 
-def _matrix_of(rec):
-    """A in the caller's numbering with Pr A Pc = L U, formed on integers: A[i, j] = (L U)[perm_r[i], perm_c[j]]; its CSC pattern is
-    the structural product (entries that cancel stay, as explicit zeros)"""
-    import scipy.sparse as sp
-    n = rec.n
-    L, U = rec.matrices(C128)
-    Lp_, Up_ = rec.matrices(pattern=True)
-    P = (Lp_ @ Up_).tocsc(); P.sort_indices()
-    V = (L @ U).tocsc()
-    pr, pc = np.asarray(rec.perm_r), np.asarray(rec.perm_c)
-    ipr = np.empty(n, int); ipr[pr] = np.arange(n); ipc = np.empty(n, int); ipc[pc] = np.arange(n)
-    Pc = P.tocoo()
-    A = sp.csc_matrix((np.ones(Pc.nnz), (ipr[Pc.row], ipc[Pc.col])), shape=(n, n)); A.sort_indices()
-    Ac = A.tocoo()
-    vals = np.asarray(V[pr[Ac.row], pc[Ac.col]]).reshape(-1).astype(C128)
-    A = sp.csc_matrix((vals + 0, (Ac.row, Ac.col)), shape=(n, n))
-    # (csc_matrix from COO drops nothing: explicit zeros are kept)
-    A.sort_indices()
-    return A
-
-
 @pytest.mark.parametrize("P", [1, 4])
 @pytest.mark.parametrize("fam", REFAC_FAMS)
 def test_lu_device_factorisation_is_exact_on_integers(na, fam, P, monkeypatch):
@@ -326,7 +307,7 @@ def test_lu_device_factorisation_is_exact_on_integers(na, fam, P, monkeypatch):
     monkeypatch.setenv("NEP_LU_WIDE_P", str(P))
     rec = lc.make_recipe(fam, "csc", "plain", "exact")
     n = rec.n
-    A = _matrix_of(rec)
+    A = lc.matrix_of(rec)
     Ap = np.ascontiguousarray(A.indptr, dtype=np.int32); Ai = np.ascontiguousarray(A.indices, dtype=np.int32)
     Ax = np.ascontiguousarray(A.data, dtype=C128)
     one = lambda z: np.abs(z.real) + np.abs(z.imag)
@@ -398,7 +379,7 @@ def test_lu_device_factorisation_refuses_patterns_that_are_not_closed(na, fam):
     _lib, lib, st = _L()
     hp = _lib.hptr
     rec = lc.make_recipe(fam, "csc", "plain", "exact")
-    A = _matrix_of(rec)
+    A = lc.matrix_of(rec)
     Ap = np.ascontiguousarray(A.indptr, dtype=np.int32); Ai = np.ascontiguousarray(A.indices, dtype=np.int32)
     ref = create(rec)
     plan = C.c_void_p()
@@ -411,6 +392,202 @@ def test_lu_device_factorisation_refuses_patterns_that_are_not_closed(na, fam):
         lib.nep_lu_destroy(ref)
 
 
+# ---- the device factorisation on closed fill patterns (lu_checkers.REFAC_CLOSED): wide levels with sparse tops ----------------------
+CLOSED = list(lc.REFAC_CLOSED)
+SCHED_ENV = ("NEP_ML_BMAX", "NEP_ML_SPLIT", "NEP_ML_CHUNK", "NEP_ML_BLK_RHS", "NEP_ML_BLK_RHS_MIN", "NEP_ML_APEX", "NEP_NO_GRAPH", "NEP_ML_FUSE",
+             "NEP_LU_SCHED", "NEP_LU_WIDE_P", "NEP_LU_DEV_MAXPROD")
+NSOLVES = 10                                                # expected_solves of every factor call and of the handles they are compared with
+_OPS = {}
+
+
+class RefacPlan:
+    """one plan of a closed family for panels of P (NEP_LU_WIDE_P and the family's block maximum are read when the reference handle
+    and the plan are created), the three factor calls on it, and the handles they return (destroyed on exit)"""
+
+    def __init__(self, fam, P, monkeypatch):
+        for k in SCHED_ENV:
+            monkeypatch.delenv(k, raising=False)
+        if P is not None:
+            monkeypatch.setenv("NEP_LU_WIDE_P", str(P))
+        if lc.REFAC_CLOSED[fam][2]:
+            monkeypatch.setenv("NEP_ML_BMAX", str(lc.REFAC_CLOSED[fam][2]))
+        self.fam, self.P = fam, P
+        self.inp = lc.refac_inputs(fam, "exact")
+        self.rec, self.pl = self.inp["rec"], self.inp["plan"]
+        self.nL, self.nU = len(self.rec.Lx), len(self.rec.Ux)
+        self.ref, self.plan, self.handles = None, C.c_void_p(), []
+
+    def __enter__(self):
+        _lib, lib, st = _L()
+        hp, rec, pl = _lib.hptr, self.rec, self.pl
+        _lib.check(lib.nep_lu_set_expected_solves(NSOLVES))
+        self.ref = create(lc.make_closed_recipe(self.fam, "rounded"))      # any values of the pattern: the plan is symbolic
+        _lib.check(lib.nep_lu_refac_create(self.ref, rec.n, hp(rec.Lp), hp(rec.Li), hp(rec.Up), hp(rec.Ui), hp(rec.perm_r), hp(rec.perm_c),
+                                           hp(pl.Ap), hp(pl.Ai), C.byref(self.plan)))
+        return self
+
+    def __exit__(self, *exc):
+        _lib, lib, st = _L()
+        for h in self.handles:
+            if h.value:
+                lib.nep_lu_destroy(h)
+        if self.plan.value:
+            lib.nep_lu_refac_destroy(self.plan)
+        if self.ref is not None:
+            lib.nep_lu_destroy(self.ref)
+        lib.nep_lu_set_expected_solves(50)                   # the default of the header
+        return False
+
+    def assert_not_vacuous(self):
+        """the plan holds the product classes of classify_products and, for P >= 2, its records, deferred products and launches"""
+        _lib, lib, st = _L()
+        pl, P = self.pl, self.P
+        ri = (C.c_int64 * 6)(); _lib.check(lib.nep_lu_refac_info(self.plan, ri))
+        wi = (C.c_int64 * 5)(); _lib.check(lib.nep_lu_refac_wide_info(self.plan, wi))
+        ri, wi = list(ri), list(wi)
+        assert ri[0] == pl.n and ri[1:5] == pl.counts[:4] and ri[1] - ri[2] - ri[3] == pl.counts[4] > 0, (ri, pl.counts)
+        assert wi[0] == P and wi[1] == pl.counts[5], (wi, pl.counts)
+        if P >= 2:
+            info = pl.panels(P)["info"]
+            assert wi[3] == info["records"] > 0 and wi[4] == info["deferred"] > 0 and wi[2] == info["launches"], (wi, info)
+            assert wi[2] <= info["panel_steps"] + (P - 1) * info["wide_levels"], (wi, info)
+        else:
+            assert wi[2] == wi[1] and wi[3] == wi[4] == 0, wi
+
+    def factor(self, name, data, limit=1e8, want_rc=0):
+        """one call: (Lx, Ux, health, handles), a batch axis first; Lx, Ux None for the terms call"""
+        _lib, lib, st = _L()
+        hp = _lib.hptr
+        nF = self.nL + self.nU
+        if name == "nep_lu_factor_dev":
+            LU = np.full(nF, SENT, dtype=C128); health = np.full(3, -1.0); out = C.c_void_p()
+            rc = lib.nep_lu_factor_dev(self.plan, hp(np.ascontiguousarray(data)), NSOLVES, limit, hp(health), hp(LU), C.byref(out), st())
+            outs, LU, health = [out], LU[None, :], health[None, :]
+        else:
+            B = len(data[1]) if isinstance(data, tuple) else len(data)
+            health = np.full((B, 3), -1.0); arr = (C.c_void_p * B)()
+            if isinstance(data, tuple):
+                D, Cf = data
+                Dd = _up(np.ascontiguousarray(D).reshape(-1))                 # nnz(A) x mt, entry-major
+                rc = lib.nep_lu_factor_dev_batch_terms(self.plan, B, _p(Dd), D.shape[1], hp(np.ascontiguousarray(Cf)), NSOLVES, limit, hp(health), arr, st())
+                LU = None
+            else:
+                LU = np.full((B, nF), SENT, dtype=C128)
+                rc = lib.nep_lu_factor_dev_batch(self.plan, B, hp(np.ascontiguousarray(data)), NSOLVES, limit, hp(health), hp(LU), arr, st())
+            outs = [C.c_void_p(arr[b]) for b in range(B)]
+        self.handles += outs
+        assert rc == want_rc, (name, rc, lib.nep_last_error())
+        return (None if LU is None else LU[:, :self.nL]), (None if LU is None else LU[:, self.nL:]), health, outs
+
+    def assert_solves_like_created(self, h, rec, Lx, Ux, kind, key):
+        """eight solves on the returned handle and on a handle nep_lu_create_csc builds from the same arrays: the same bits"""
+        _lib, lib, st = _L()
+        assert h.value, key
+        if (self.fam, kind) not in _OPS:
+            _OPS[self.fam, kind] = lc.make_ops(lc.refac_inputs(self.fam, kind)["rec"], kind, 11, [1, 5, 8, 33, 2, 3, 9, 4])
+        hc = create(rec, Lx, Ux)
+        try:
+            for k, op in enumerate(_OPS[self.fam, kind]):
+                got, want = run_op(h, op), run_op(hc, op)
+                assert np.array_equal(got.view(np.float64), want.view(np.float64), equal_nan=True), \
+                    "%s %s P=%s: solve %d (nrhs %d) differs from the created handle's in %d values" % (
+                        key, self.fam, self.P, k, op.nrhs, int(np.sum(got.view(np.float64) != want.view(np.float64))))
+        finally:
+            lib.nep_lu_destroy(hc)
+        _count("refac %s %s" % (self.fam, key), kind, len(_OPS[self.fam, kind]))
+
+
+@pytest.mark.parametrize("P", lc.LU_WIDE_PS)
+@pytest.mark.parametrize("fam", CLOSED)
+def test_lu_device_factorisation_on_closed_fill_patterns(na, fam, P, monkeypatch):
+    """closures of an arrow, a two-tier pattern and a random-ancestor tree (symmetric and with U != L^T), banded grids, a tree whose
+    level 1 is not wide: nep_lu_factor_dev, the batch of three and the batch from three terms, step by step and in panels of 2, 3, 4.
+    Exact values: L, U and the health words bit for bit, the same bits from a second call; rounded values: the componentwise
+    residual bound of lu_checkers.refac_check.  Every returned handle solves bit for bit like a handle created from the same
+    values, and the plan reports the product classes, records, deferred products and launches of the NumPy restatement"""
+    with RefacPlan(fam, P, monkeypatch) as rp:
+        rp.assert_not_vacuous()
+        for kind in ("exact", "rounded"):
+            forms = lc.refac_forms(fam, kind)
+            last = {}
+
+            def impl(name, rec, data, P_):
+                Lx, Ux, health, outs = rp.factor(name, data)
+                want = forms[name][1]
+                if Lx is not None:
+                    Lx2, Ux2, health2, _ = rp.factor(name, data)
+                    assert all(np.array_equal(a.view(np.float64), b.view(np.float64)) for a, b in ((Lx, Lx2), (Ux, Ux2), (health, health2))), \
+                        "%s: a second call on the plan returned other bits" % name
+                    last["LU"] = (Lx, Ux)
+                elif kind == "rounded":
+                    # the assembly of these terms is exact: the very matrices of the batch, so the very factors and health words
+                    hb = last["health"]
+                    assert np.array_equal(health.view(np.int64), hb.view(np.int64)), (name, health, hb)
+                for b, (rb, _) in enumerate(want):
+                    vals = (Lx[b], Ux[b]) if Lx is not None else (rb.Lx, rb.Ux) if kind == "exact" else (last["LU"][0][b], last["LU"][1][b])
+                    rp.assert_solves_like_created(outs[b], rb, vals[0], vals[1], kind, name)
+                last["health"] = health
+                return Lx, Ux, health
+            assert lc.refac_check(impl, fam, kind, P) == 7
+
+
+BREAK_FAMS = ["arrow/m300_t41/unsym", "tree/bin11_p0.3/bmax8", "grid/24x24"]
+
+
+@pytest.mark.parametrize("P", lc.LU_WIDE_PS)
+@pytest.mark.parametrize("fam", BREAK_FAMS)
+def test_lu_device_factorisation_reports_a_broken_pivot_and_keeps_the_rest_of_the_batch(na, fam, P, monkeypatch):
+    """exact factors with one U_kk = 0 -- k inside a level-0 block (k_lu_int), the first pivot and a later slot of a panel (k_lu_scale
+    after the panel's own elimination), pivot n - 1 -- and a matrix with a NaN entry.  The single call: NEP_ERR_SINGULAR, no handle,
+    health[0] = 1.  A batch with the broken matrix in the middle: its handle NULL, the two others exact in values, health and solves
+    (the batched schedule build with two accepted members that are not adjacent); a batch with one good member in the middle: that
+    one exact (the single-factor build).  A zero pivot is a floating-point division by zero: nothing here faults"""
+    with RefacPlan(fam, P, monkeypatch) as rp:
+        inp = rp.inp
+        rec, rec2, Ax, Ax2 = inp["rec"], inp["rec2"], inp["Ax"], inp["Ax2"]
+        case = pc.Case(fam, "P=%d" % P, "exact", None)
+
+        def good(tag, b, Lx, Ux, health, outs, r_, A_):
+            pc.assert_exact(tag + " L", case, Lx[b], r_.Lx)
+            pc.assert_exact(tag + " U", case, Ux[b], r_.Ux)
+            pc.assert_exact(tag + " health", case, health[b], lc.expected_health(r_, A_))
+            rp.assert_solves_like_created(outs[b], r_, Lx[b], Ux[b], "exact", "batch with a broken member")
+        for label, k, Abad in lc.breakdown_cases(fam, P):
+            tag = "%s (pivot %d)" % (label, k)
+            _, _, health, outs = rp.factor("nep_lu_factor_dev", Abad, want_rc=-3)          # NEP_ERR_SINGULAR
+            assert not outs[0].value and health[0][0] == 1.0, (tag, health)
+            Lx, Ux, health, outs = rp.factor("nep_lu_factor_dev_batch", np.stack([Ax, Abad, Ax2]))
+            assert not outs[1].value and health[1][0] == 1.0, (tag, health)
+            good(tag + " batch[0]", 0, Lx, Ux, health, outs, rec, Ax)
+            good(tag + " batch[2]", 2, Lx, Ux, health, outs, rec2, Ax2)
+            Lx, Ux, health, outs = rp.factor("nep_lu_factor_dev_batch", np.stack([Abad, Ax2, Abad]))
+            assert not outs[0].value and not outs[2].value and health[0][0] == 1.0 and health[2][0] == 1.0, (tag, health)
+            good(tag + " the one good member", 1, Lx, Ux, health, outs, rec2, Ax2)
+
+
+@pytest.mark.parametrize("kind", ["exact", "rounded"])
+def test_lu_device_factorisation_growth_limit_between_the_health_words(na, kind, monkeypatch):
+    """a factor is refused when max |L| or max |U| / max |A| exceeds the limit: with the limit at the larger of the two words the
+    factor is accepted, one unit in the last place below it is refused (NEP_ERR_SINGULAR, no handle, the same health words, no
+    broken pivot) -- exact values: max |L| = 1 above the growth; rounded (dominant diagonal): the growth above max |L|"""
+    fam = "arrow/m300_t41/unsym"
+    with RefacPlan(fam, None, monkeypatch) as rp:
+        data, want = lc.refac_forms(fam, kind)["nep_lu_factor_dev"]
+        Lx, Ux, health, outs = rp.factor("nep_lu_factor_dev", data)
+        h = health[0]
+        pc.assert_exact("health", pc.Case(fam, "growth", kind, None), h, lc.expected_health(lc.with_values(want[0][0], Lx[0], Ux[0]), data))
+        assert (h[1] > h[2]) == (kind == "exact") and h[1] != h[2], h
+        hi = float(max(h[1], h[2]))
+        _, _, h2, outs = rp.factor("nep_lu_factor_dev", data, limit=hi)
+        assert outs[0].value and np.array_equal(h2[0], h)
+        below = float(np.nextafter(hi, 0.0))
+        assert below > min(h[1], h[2])
+        _, _, h3, outs = rp.factor("nep_lu_factor_dev", data, limit=below, want_rc=-3)
+        assert not outs[0].value and np.array_equal(h3[0], h) and h3[0][0] == 0.0, (h3, h)
+        _, _, h4, outs = rp.factor("nep_lu_factor_dev_batch", np.stack([data, data]), limit=below)
+        assert not outs[0].value and not outs[1].value and np.array_equal(h4[0], h) and np.array_equal(h4[1], h)
+
+
 def test_zz_report_counts_and_largest_ratios(na):
     """calls checked per entry point / handle treatment / schedule shape (exact, rounded), and the largest |dev - ref| / bound of the
     rounded cases of every family that ran in this process (each was asserted <= 1 where it arose)"""
@@ -421,3 +598,4 @@ def test_zz_report_counts_and_largest_ratios(na):
             print("ratio %-28s %.3g" % (name, pc.RATIOS[name]))
             assert pc.RATIOS[name] <= 1.0
     print("bound constant: measured r = %.4g, c = 2^%d" % (lc.R_MEASURED, int(np.log2(lc.C_BLOCK))))
+    print("factorisation residual constant: measured r = %.4g, c = 2^%d" % (lc.R_REFAC_MEASURED, int(np.log2(lc.C_REFAC))))
