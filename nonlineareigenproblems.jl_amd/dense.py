@@ -143,6 +143,12 @@ def copy(src, dst, length=None):
     check(lib.nep_dev_copy(c_vp(dst.data_ptr()), c_vp(src.data_ptr()), 16 * (length if length is not None else src.numel()), stream_ptr()))
 
 
+def zgemm(ta, tb, m, n, k, alpha, A, lda, B, ldb, beta, Cm, ldc):
+    """Cm = alpha op(A) op(B) + beta Cm on column-major device blocks; op codes 0 none / 1 transpose / 2 conjugate transpose"""
+    check(lib.nep_zgemm(ta, tb, m, n, k, _lib.cd(alpha), c_vp(A.data_ptr()), lda, c_vp(B.data_ptr()), ldb, _lib.cd(beta),
+                        c_vp(Cm.data_ptr()), ldc, stream_ptr()))
+
+
 class ColMajorBlock:
     """a Ritz block kept COLUMN-major: `t` is a device (k, rows) tensor = rows x k column-major (what nep_gemm_ts writes with
     y_rowmajor = 0).  Large sparse problems use it for their convergence checks: the tiled residual kernel then reads every

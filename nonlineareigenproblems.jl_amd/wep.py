@@ -10,11 +10,16 @@ rank-one nz x nz blocks (2 nz^3 = 2e9 non-zeros at nz = 999).  Here the NEP is
 i.e. three big REAL sparse matrices in one stacked CSR (the HBM-bound part) plus a factored corner term applied as
 two small dense products with Rm (nz x nz, the scaled DFT matrix of Waveguide.jl:53-65).
 """
+import ctypes as C
 
 import numpy as np
 import scipy.sparse as sp
+import torch
 
-from . import funcs
+from . import _lib, funcs
+from ._env import env_str
+from ._lib import lib, check, hptr, c_vp
+from .nep import AbstractSPMF, CDT, to_dev, to_host, is_dev, stream_ptr
 
 
 def generate_fd_interior_mat(nx, nz, hx, hz):
@@ -117,12 +122,9 @@ class WaveguideData:
 # =================================================================================================
 # device NEP
 
-import torch
-
-from . import _lib
-from ._env import env_str
-from ._lib import lib, check, hptr, c_vp
-from .nep import AbstractSPMF, CDT, to_dev, to_host, is_dev, stream_ptr
+def _p(t, skip=0):
+    """address of a device tensor, or a raw device address, `skip` complex entries further on"""
+    return c_vp((t.data_ptr() if is_dev(t) else int(t)) + 16 * skip)
 
 
 def _corner_derivs(wd, lam, k, scale=1.0):
@@ -160,6 +162,27 @@ def _corner_values(wd, lams):
     return 1j * (sg * s0) + wd.d0
 
 
+class _PendingResid:
+    """an enqueued residual batch: get() runs finish(*parts), the synchronising read-backs, once.  With defer=False that happens
+    here (the layouts whose checks are not deferred); otherwise an event marks the end of the enqueued work for ready()"""
+
+    def __init__(self, finish, parts, defer):
+        self.finish, self.parts, self.result, self.ev = finish, parts, None, None
+        if defer:
+            self.ev = torch.cuda.Event(); self.ev.record()
+        else:
+            self.get()
+
+    def ready(self):
+        return self.result is not None or self.ev.query()
+
+    def get(self):
+        if self.result is None:
+            self.result = self.finish(*self.parts)
+            self.parts = None
+        return self.result
+
+
 class WEP(AbstractSPMF):
     """Waveguide eigenvalue problem on the device: 3 real sparse terms (stacked CSR / SELL) + factored corner.
     Mirrors `nep_gallery(WEP, nx=, nz=, benchmark_problem=, neptype=, delta=)` (GalleryWaveguide.jl:60-94); both
@@ -185,13 +208,13 @@ class WEP(AbstractSPMF):
         """nep_wep_pinv handle (prime-factor DFT plan + bb on the device) for P(lam)^{-1}, or None (nz too large:
         the dense R matrices are used instead)"""
         if getattr(self, "_pinv_h", False) is False:
-            self._pinv_h = None
-            import ctypes as C
             _lib.require_gpu()
             h = c_vp()
             bb = np.ascontiguousarray(self.wd.bb, dtype=np.complex128)
-            if lib.nep_wep_pinv_create(self.nz, hptr(bb), C.byref(h)) == 0:
-                self._pinv_h = h
+            st = lib.nep_wep_pinv_create(self.nz, hptr(bb), C.byref(h))
+            if st != _lib.NEP_ERR_UNSUPPORTED:
+                check(st)                                   # a HIP error or a refused argument is no "nz too large"
+            self._pinv_h = h if st == 0 else None
         return self._pinv_h
 
     def _corner_dev(self):
@@ -207,21 +230,38 @@ class WEP(AbstractSPMF):
         Dtab: device tensor (k, 2nz) = column-major 2nz x k table (1/nz already folded in)."""
         Rm, RmH = self._corner_dev()
         nz, N = self.nz, self.N
-        va = V.data_ptr() if is_dev(V) else V
         st = stream_ptr()
         P = torch.empty((k, nz), dtype=CDT, device="cuda")
         t = torch.empty(nz, dtype=CDT, device="cuda")
         y = torch.empty(nz, dtype=CDT, device="cuda")
         for half in (0, 1):
             row0 = N + half * nz
-            check(lib.nep_gemm_ts_dev(c_vp(RmH.data_ptr()), nz, nz, nz, c_vp(va + 16 * row0), ldv, 0, k,
-                                      c_vp(P.data_ptr()), nz, 0, st))
-            check(lib.nep_rowdot(nz, k, c_vp(P.data_ptr()), nz, c_vp(Dtab.data_ptr() + 16 * half * nz), 2 * nz,
-                                 c_vp(t.data_ptr()), st))
-            check(lib.nep_gemm_ts_dev(c_vp(Rm.data_ptr()), nz, nz, nz, c_vp(t.data_ptr()), nz, 0, 1,
-                                      c_vp(y.data_ptr()), nz, 0, st))
-            check(lib.nep_axpy(nz, _lib.cd(1.0), c_vp(y.data_ptr()), c_vp(z.data_ptr() + 16 * row0), st))
+            check(lib.nep_gemm_ts_dev(_p(RmH), nz, nz, nz, _p(V, row0), ldv, 0, k, _p(P), nz, 0, st))
+            check(lib.nep_rowdot(nz, k, _p(P), nz, _p(Dtab, half * nz), 2 * nz, _p(t), st))
+            check(lib.nep_gemm_ts_dev(_p(Rm), nz, nz, nz, _p(t), nz, 0, 1, _p(y), nz, 0, st))
+            check(lib.nep_axpy(nz, _lib.cd(1.0), _p(y), _p(z, row0), st))
         return z
+
+    def _add_corner(self, la, Q, ldq, R, rowmajor):
+        """R += blkdiag(Rm, Rm) diag(s(lam_s)) blkdiag(Rm, Rm)^H Q[N:, s] / nz for the k = len(la) columns: the corner term
+        (Waveguide.jl:351-374) on the 2 nz boundary rows.  Q: the n x k block with leading dimension ldq, R: its 2 nz boundary
+        residual rows (row-major: (2 nz, k); column-major: (k, 2 nz)), both in the layout the flag names"""
+        Rm, RmH = self._corner_dev()
+        nz, N, k = self.nz, self.N, len(la)
+        st = stream_ptr()
+        Sd = to_dev(_corner_values(self.wd, la) / nz)                 # 2nz x k
+        P = torch.empty((k, nz), dtype=CDT, device="cuda")
+        Y = torch.empty((nz, k) if rowmajor else (k, nz), dtype=CDT, device="cuda")
+        for half in (0, 1):
+            row0 = N + half * nz
+            check(lib.nep_gemm_ts_dev(_p(RmH), nz, nz, nz, _p(Q, row0 * ldq if rowmajor else row0), ldq, int(rowmajor), k,
+                                      _p(P), nz, 0, st))
+            check(lib.nep_hadamard(nz, k, _p(P), nz, _p(Sd, half * nz), 2 * nz, st))
+            check(lib.nep_gemm_ts_dev(_p(Rm), nz, nz, nz, _p(P), nz, 0, k, _p(Y), k if rowmajor else nz, int(rowmajor), st))
+            if rowmajor:
+                check(lib.nep_axpy(nz * k, _lib.cd(1.0), _p(Y), _p(R, half * nz * k), st))
+            else:
+                R[:, half * nz:(half + 1) * nz] += Y
 
     # ---- driver hooks
     def derivative_table(self, sigma, m, rowscale=None):
@@ -265,10 +305,10 @@ class WEP(AbstractSPMF):
             self._absx = torch.empty(2 * nz, dtype=CDT, device="cuda")
         nz, N = self.nz, self.N
         st = stream_ptr()
-        check(lib.nep_absvec(2 * nz, c_vp(x.data_ptr() + 16 * N), c_vp(self._absx.data_ptr()), st))
+        check(lib.nep_absvec(2 * nz, _p(x, N), _p(self._absx), st))
         for half in (0, 1):
-            check(lib.nep_gemm_ts_dev(c_vp(self._Pabs[half].data_ptr()), nz, nz, nz, c_vp(self._absx.data_ptr() + 16 * half * nz),
-                                      nz, 0, 1, c_vp(self._den.data_ptr() + 16 * (N + half * nz)), nz, 0, st))
+            check(lib.nep_gemm_ts_dev(_p(self._Pabs[half]), nz, nz, nz, _p(self._absx, half * nz), nz, 0, 1,
+                                      _p(self._den, N + half * nz), nz, 0, st))
         return self._den
 
     def corner_matrix(self, lam, i=0):
@@ -299,99 +339,73 @@ class WEP(AbstractSPMF):
             M = M - sp.bmat([[sp.csc_matrix((N, N)), None], [None, corner_spmf]], format="csc")
         return sp.csc_matrix(M + Cn)
 
+    # ---- residual batches: per layout of Q an enqueue part (device work only) and a finish part (the synchronising read-backs)
     def resid_norms_async(self, lams, QT):
-        """enqueues the residual batch and the corner term; the returned object's get() runs the two synchronising read-backs
-        (tiar's deferred convergence checks: the host prepares check k + 1 while the device works on check k)"""
-        from .nep import PendingNorms
-        if hasattr(QT, "cpu_matrix") or env_str("NEP_WEP_RESID_SPLIT", "1") == "0":
-            return PendingNorms(result=self.resid_norms(lams, QT))
-        fin = self.resid_norms(lams, QT, _defer=True)
-        ev = torch.cuda.Event(); ev.record()
-
-        class _P:
-            def __init__(s_):
-                s_.result = None
-            def ready(s_):
-                return s_.result is not None or ev.query()
-            def get(s_):
-                if s_.result is None:
-                    s_.result = fin()
-                return s_.result
-        return _P()
-
-    def resid_norms(self, lams, QT, _defer=False):
-        """(||M(lam_s) q_s||, ||q_s||, F) for the k columns of the row-major block QT.  ONE pass over the three sparse terms
-        (nep_resid_split_dev) gives the squared norms of the SPMF residual over the N interior rows, the squared norms of Q
-        and the residual rows of the 2 nz boundary unknowns; the dense corner term (Waveguide.jl:351-374) is added to that
-        2 nz x k block only.  (Until round 3 the whole n x k residual block was written, the corner added, and two column-norm
-        kernels read both blocks again: four times the bytes of Q per check.  NEP_WEP_RESID_SPLIT=0 keeps that form.)"""
+        """enqueues the residual batch and the corner term (Waveguide.jl:351-374, added to the 2 nz boundary rows only); the
+        returned object's get() gives (||M(lam_s) q_s||, ||q_s||, F) for the k columns of QT.  The row-major split form is
+        deferred (tiar's deferred convergence checks: the host prepares check k + 1 while the device works on check k);
+        the column-major form and NEP_WEP_RESID_SPLIT=0 finish here"""
         la = np.asarray(lams, dtype=np.complex128)
-        k = len(la)
-        F = np.empty((3, k), dtype=np.complex128, order="F")
+        F = np.empty((3, len(la)), dtype=np.complex128, order="F")
         for i, f in enumerate(self.fi):
             F[i, :] = f.values(la)
-        n, nz, N = self.n, self.nz, self.N
-        st = stream_ptr()
         if hasattr(QT, "cpu_matrix"):
-            # column-major Ritz block (dense.ColMajorBlock, device (k, n)): tiled K2 with contiguous column loads; the
-            # residual rows of the 2 nz boundary unknowns come back column-major and take the corner term
-            Qc = QT.t
-            tail = torch.empty((k, 2 * nz), dtype=CDT, device="cuda")
-            out = self.dev.resid_batch_cm(F, Qc, k, row0=N, tail=tail)
-            Rm, RmH = self._corner_dev()
-            S = _corner_values(self.wd, la) / nz
-            Sd = to_dev(S)
-            P = torch.empty((k, nz), dtype=CDT, device="cuda")
-            Y = torch.empty((k, nz), dtype=CDT, device="cuda")
-            for half in (0, 1):
-                row0 = N + half * nz
-                check(lib.nep_gemm_ts_dev(c_vp(RmH.data_ptr()), nz, nz, nz, c_vp(Qc.data_ptr() + 16 * row0), n, 0, k,
-                                          c_vp(P.data_ptr()), nz, 0, st))
-                check(lib.nep_hadamard(nz, k, c_vp(P.data_ptr()), nz, c_vp(Sd.data_ptr() + 16 * half * nz), 2 * nz, st))
-                check(lib.nep_gemm_ts_dev(c_vp(Rm.data_ptr()), nz, nz, nz, c_vp(P.data_ptr()), nz, 0, k,
-                                          c_vp(Y.data_ptr()), nz, 0, st))
-                tail[:, half * nz:(half + 1) * nz] += Y
-            tn2 = (tail.real ** 2 + tail.imag ** 2).sum(dim=1)
-            o = out.cpu().numpy()
-            return np.sqrt(o[:k] + tn2.cpu().numpy()), np.sqrt(o[k:]), F
-        ldq = QT.shape[1]
-        split = env_str("NEP_WEP_RESID_SPLIT", "1") != "0"
-        if split:
-            out = torch.zeros(2 * k, dtype=torch.float64, device="cuda")
-            RT = torch.empty((2 * nz, k), dtype=CDT, device="cuda")                 # residual rows N .. n-1 only
-            check(lib.nep_resid_split_dev(self.dev.h, k, hptr(F), c_vp(QT.data_ptr()), ldq, N, c_vp(out.data_ptr()),
-                                          c_vp(RT.data_ptr()), k, st))
-            tail0 = 0
-        else:
-            RT = torch.empty((n, k), dtype=CDT, device="cuda")
-            check(lib.nep_resid_block(self.dev.h, k, hptr(F), c_vp(QT.data_ptr()), ldq, c_vp(RT.data_ptr()), k, st))
-            tail0 = N
-        # corner: R[N:, s] += Rfull diag(s(lam_s)) Rfull^H Q[N:, s] / nz
-        Rm, RmH = self._corner_dev()
-        S = _corner_values(self.wd, la) / nz      # 2nz x k
-        Sd = to_dev(S)
-        P = torch.empty((k, nz), dtype=CDT, device="cuda")
-        Y = torch.empty((nz, k), dtype=CDT, device="cuda")
-        for half in (0, 1):
-            row0 = N + half * nz
-            check(lib.nep_gemm_ts_dev(c_vp(RmH.data_ptr()), nz, nz, nz, c_vp(QT.data_ptr() + 16 * row0 * ldq), ldq, 1, k,
-                                      c_vp(P.data_ptr()), nz, 0, st))
-            check(lib.nep_hadamard(nz, k, c_vp(P.data_ptr()), nz, c_vp(Sd.data_ptr() + 16 * half * nz), 2 * nz, st))
-            check(lib.nep_gemm_ts_dev(c_vp(Rm.data_ptr()), nz, nz, nz, c_vp(P.data_ptr()), nz, 0, k,
-                                      c_vp(Y.data_ptr()), k, 1, st))
-            check(lib.nep_axpy(nz * k, _lib.cd(1.0), c_vp(Y.data_ptr()), c_vp(RT.data_ptr() + 16 * (tail0 + half * nz) * k), st))
+            return _PendingResid(self._resid_finish_cm, self._resid_enqueue_cm(la, F, QT.t), defer=False)
+        if env_str("NEP_WEP_RESID_SPLIT", "1") == "0":
+            return _PendingResid(self._resid_finish_full, self._resid_enqueue_full(la, F, QT), defer=False)
+        return _PendingResid(self._resid_finish_split, self._resid_enqueue_split(la, F, QT), defer=True)
+
+    def resid_norms(self, lams, QT):
+        return self.resid_norms_async(lams, QT).get()
+
+    def _resid_enqueue_cm(self, la, F, Qc):
+        """column-major Ritz block (dense.ColMajorBlock, device (k, n)): tiled K2 with contiguous column loads; the residual
+        rows of the 2 nz boundary unknowns come back column-major and take the corner term"""
+        k = len(la)
+        tail = torch.empty((k, 2 * self.nz), dtype=CDT, device="cuda")
+        out = self.dev.resid_batch_cm(F, Qc, k, row0=self.N, tail=tail)
+        self._add_corner(la, Qc, self.n, tail, rowmajor=False)
+        return out, (tail.real ** 2 + tail.imag ** 2).sum(dim=1), F
+
+    @staticmethod
+    def _resid_finish_cm(out, tn2, F):
+        k = F.shape[1]
+        o = out.cpu().numpy()
+        return np.sqrt(o[:k] + tn2.cpu().numpy()), np.sqrt(o[k:]), F
+
+    def _resid_enqueue_split(self, la, F, QT):
+        """row-major block: ONE pass over the three sparse terms (nep_resid_split_dev) gives the squared norms of the SPMF
+        residual over the N interior rows, the squared norms of Q and the residual rows of the 2 nz boundary unknowns"""
+        k, st = len(la), stream_ptr()
+        out = torch.zeros(2 * k, dtype=torch.float64, device="cuda")
+        RT = torch.empty((2 * self.nz, k), dtype=CDT, device="cuda")                # residual rows N .. n-1 only
+        check(lib.nep_resid_split_dev(self.dev.h, k, hptr(F), _p(QT), QT.shape[1], self.N, _p(out), _p(RT), k, st))
+        self._add_corner(la, QT, QT.shape[1], RT, rowmajor=True)
+        return out, RT, F, st
+
+    @staticmethod
+    def _resid_finish_split(out, RT, F, st):
+        k = F.shape[1]
+        rn = np.empty(k)
+        check(lib.nep_rowmajor_colnorms(RT.shape[0], k, _p(RT), k, hptr(rn), st))       # (synchronises)
+        o = out.cpu().numpy()
+        return np.sqrt(o[:k] + rn ** 2), np.sqrt(o[k:]), F
+
+    def _resid_enqueue_full(self, la, F, QT):
+        """row-major block under NEP_WEP_RESID_SPLIT=0: the whole n x k residual block is written, the corner added, and two
+        column-norm kernels read both blocks again (four times the bytes of Q per check; the form until round 3)"""
+        k, st = len(la), stream_ptr()
+        RT = torch.empty((self.n, k), dtype=CDT, device="cuda")
+        check(lib.nep_resid_block(self.dev.h, k, hptr(F), _p(QT), QT.shape[1], _p(RT), k, st))
+        self._add_corner(la, QT, QT.shape[1], RT[self.N:], rowmajor=True)
+        return QT, RT, F, st
+
+    @staticmethod
+    def _resid_finish_full(QT, RT, F, st):
+        n, k = RT.shape
         rn = np.empty(k); qn = np.empty(k)
-        if split:
-            def finish():
-                check(lib.nep_rowmajor_colnorms(2 * nz, k, c_vp(RT.data_ptr()), k, hptr(rn), st))      # (synchronises)
-                o = out.cpu().numpy()
-                return np.sqrt(o[:k] + rn ** 2), np.sqrt(o[k:]), F
-            if _defer:
-                return finish
-            return finish()
-        else:
-            check(lib.nep_rowmajor_colnorms(n, k, c_vp(RT.data_ptr()), k, hptr(rn), st))
-            check(lib.nep_rowmajor_colnorms(n, k, c_vp(QT.data_ptr()), ldq, hptr(qn), st))
+        check(lib.nep_rowmajor_colnorms(n, k, _p(RT), k, hptr(rn), st))
+        check(lib.nep_rowmajor_colnorms(n, k, _p(QT), QT.shape[1], hptr(qn), st))
         return rn, qn, F
 
     def fro_norms(self):

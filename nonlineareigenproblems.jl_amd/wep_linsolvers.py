@@ -9,16 +9,20 @@ src/gallery_extra/waveguide/Waveguide.jl:394-567 and waveguide_preconditioner.jl
 
 Device realisation.  The interior operator A(lam) X + X B + K .* X is the interior block of the three stacked sparse terms,
 so SchurMatVec is ONE K1 call on the zero-padded vector (its last 2 nz rows are C2T v for free) + P(lam)^{-1} on 2 nz
-entries + one rectangular CSR product with C1 (nep_csr_mv).  P(lam)^{-1} = R diag(1/s(lam)) R^H / nz with the dense
-scaled-DFT matrix R (two nz x nz GEMVs).  The reference diagonalises the Sylvester operator with FFTs along z (length nz)
-and sine transforms along x (FFT length 2 (nx + 1)); here both are dense transforms -- nz x nz DFT and nx x nx sine
-matrices applied as GEMMs (nep_zgemm for the DFT, nep_dgemm on the re/im-interleaved block for the real sine matrix), 4 GEMMs
-per Sylvester solve: at nz = 999 = 27 * 37 and 2 (nx + 1) = 2008 = 8 * 251 a 4-8 GFLOP GEMM on the FP64 matrix cores (0.1 ms)
-costs less than a mixed-radix FFT would save.  The
-region sums / expansions of the SMW correction are products with 0/1 indicator matrices (small GEMMs), the mm x mm SMW
-matrix is inverted once on the host and applied as a GEMV, so one preconditioner application never synchronises.
+entries + one rectangular CSR product with C1 (nep_csr_mv); with a P^{-1} plan the whole product is matrix-free (five-point
+stencil, nep_wep_schur_matvec).  P(lam)^{-1} = R diag(1/s(lam)) R^H / nz with the scaled-DFT matrix R: a prime-factor DFT
+plan (nep_wep_pinv_apply), or two nz x nz GEMVs with the dense R where nz is too large for the plan.
+
+The reference diagonalises the Sylvester operator with FFTs along z (length nz) and sine transforms along x; here the
+Sylvester solve (nep_wep_sylv_solve, csrc/wep.hip) is a prime-factor DFT along z plus one tridiagonal solve per z-mode along
+x, and it takes every grid the constructor admits (nx = nz + 4 <= 2048).  The region means and the expansion of the SMW
+correction are region kernels (nep_wep_region_means / nep_wep_region_expand); the mm x mm SMW matrix is inverted once on the
+device and applied as a GEMV, so one preconditioner application never synchronises.  Which form of the correction runs is
+fixed when the preconditioner is built (WEPPreconditioner._fused): the three-transform form (nep_wep_smw_apply, with the
+set-up in mode space) where nep_wep_plan has one for the grid, otherwise the piecewise form (four transforms).
 """
 import ctypes as C
+import inspect
 
 import numpy as np
 import scipy.sparse as sp
@@ -28,18 +32,10 @@ from . import _lib, dense
 from ._env import env_str
 from ._lib import lib, check, c_vp
 from .linsolvers import DeviceLU, FactorizeLinSolver, GMRESLinSolver, LinSolver, LinSolverCreator
-from .nep import CDT, DeviceCSR, to_dev, to_host, is_dev, stream_ptr
-from .wep import WEP, _corner_derivs
+from .nep import CDT, DeviceCSR, to_dev, to_host, stream_ptr
+from .wep import WEP, _corner_derivs, _p
 
-N_, T_, C_ = 0, 1, 2          # op codes of nep_zgemm
-
-
-def _p(t):
-    return c_vp(t.data_ptr() if is_dev(t) else int(t))
-
-
-def zgemm(ta, tb, m, n, k, alpha, A, lda, B, ldb, beta, Cm, ldc):
-    check(lib.nep_zgemm(ta, tb, m, n, k, _lib.cd(alpha), _p(A), lda, _p(B), ldb, _lib.cd(beta), _p(Cm), ldc, stream_ptr()))
+PLAN_SMW = 2                  # NEP_WEP_PLAN_SMW of nep_wep_plan
 
 
 def _boundary_csr(nep):
@@ -81,53 +77,47 @@ class SchurOps:
         self.u = torch.empty(2 * self.nz, dtype=CDT, device="cuda")
         self.w = torch.empty(2 * self.nz, dtype=CDT, device="cuda")
 
-    def pinv(self, x, out):
-        """out = blkdiag(R, R) diag(1/s(lam)) blkdiag(R, R)^H x / nz   (Waveguide.jl:159-162); x, out: device addresses of
-        2 nz entries (minus block, plus block); two A^H x products per block (nep_gemv_hd), the diagonal scaling fused into
-        the first one; the work vector self.w is used"""
+    def pinv(self, x, out, xskip=0, oskip=0):
+        """out = blkdiag(R, R) diag(1/s(lam)) blkdiag(R, R)^H x / nz   (Waveguide.jl:159-162); x, out: tensors or device addresses,
+        the 2 nz entries (minus block, plus block) start xskip / oskip entries in.  Without a P^{-1} plan: two A^H x products per
+        block (nep_gemv_hd), the diagonal scaling fused into the first one; the work vector self.w is used"""
         nz = self.nz
-        xa = x.data_ptr() if is_dev(x) else x
-        oa = out.data_ptr() if is_dev(out) else out
         st = stream_ptr()
         plan = self.nep._pinv_plan()
         if plan is not None:
-            check(lib.nep_wep_pinv_apply(plan, c_vp(self.sinv.data_ptr()), c_vp(xa), c_vp(oa), st))
+            check(lib.nep_wep_pinv_apply(plan, _p(self.sinv), _p(x, xskip), _p(out, oskip), st))
             return
         for half in (0, 1):
-            o = 16 * half * nz
-            check(lib.nep_gemv_hd(c_vp(self.Rm.data_ptr()), nz, nz, nz, c_vp(xa + o), c_vp(self.sinv.data_ptr() + o),
-                                  c_vp(self.w.data_ptr() + o), st))                         # w = (1/(nz s)) .* (R^H x)
-            check(lib.nep_gemv_hd(c_vp(self.RmH.data_ptr()), nz, nz, nz, c_vp(self.w.data_ptr() + o), None, c_vp(oa + o), st))   # (R^H)^H w
+            o = half * nz
+            check(lib.nep_gemv_hd(_p(self.Rm), nz, nz, nz, _p(x, xskip + o), _p(self.sinv, o), _p(self.w, o), st))    # w = (1/(nz s)) .* (R^H x)
+            check(lib.nep_gemv_hd(_p(self.RmH), nz, nz, nz, _p(self.w, o), None, _p(out, oskip + o), st))     # (R^H)^H w
 
     def matvec(self, v, out):
         """out = vec(A(lam) X + X B + K .* X) - C1 P(lam)^{-1} C2T v   (SchurMatVec, Waveguide.jl:398-406)"""
         N, n = self.N, self.n
         if self.stencil is not None and v.data_ptr() != out.data_ptr():
             st = self.stencil
-            check(lib.nep_wep_schur_matvec(self.nep._pinv_plan(), c_vp(self.sinv.data_ptr()), self.nx, _p(v), _p(st["D0"]), st["cp"], st["cm"],
-                                           st["cx"], st["d1"], st["d2"], st["c1s"], c_vp(self.t.data_ptr()), _p(out), stream_ptr()))
+            check(lib.nep_wep_schur_matvec(self.nep._pinv_plan(), _p(self.sinv), self.nx, _p(v), _p(st["D0"]), st["cp"], st["cm"],
+                                           st["cx"], st["d1"], st["d2"], st["c1s"], _p(self.t), _p(out), stream_ptr()))
             return out
-        check(lib.nep_dev_copy(c_vp(self.pad.data_ptr()), _p(v), 16 * N, stream_ptr()))
+        check(lib.nep_dev_copy(_p(self.pad), _p(v), 16 * N, stream_ptr()))
         self.nep.dev.mlincomb_dev(self.coef, 1, 1, self.pad.data_ptr(), n, self.z)      # no host->device copy: graph-safe
-        self.pinv(self.z.data_ptr() + 16 * N, self.t)
+        self.pinv(self.z, self.t, xskip=N)
         self.C1.mv(-1.0, self.t, 1.0, self.z, out)
         return out
 
     def eliminate(self, x, rhs):
         """rhs = x_int - C1 P^{-1} x_ext   (Waveguide.jl:559-561)"""
-        xa = x.data_ptr() if is_dev(x) else x
-        self.pinv(xa + 16 * self.N, self.t)
-        self.C1.mv(-1.0, self.t, 1.0, xa, rhs)
+        self.pinv(x, self.t, xskip=self.N)
+        self.C1.mv(-1.0, self.t, 1.0, x, rhs)
         return rhs
 
     def recover(self, q, x, out):
         """out = [q; P^{-1}(x_ext - C2T q)]   (Waveguide.jl:565)"""
-        xa = x.data_ptr() if is_dev(x) else x
-        oa = out.data_ptr() if is_dev(out) else out
-        self.C2T.mv(-1.0, q, 1.0, xa + 16 * self.N, self.u)
-        self.pinv(self.u, oa + 16 * self.N)
-        if q.data_ptr() != oa:
-            check(lib.nep_dev_copy(c_vp(oa), c_vp(q.data_ptr()), 16 * self.N, stream_ptr()))
+        self.C2T.mv(-1.0, q, 1.0, _p(x, self.N).value, self.u)
+        self.pinv(self.u, out, oskip=self.N)
+        if q.data_ptr() != _p(out).value:
+            check(lib.nep_dev_copy(_p(out), _p(q), 16 * self.N, stream_ptr()))
         return out
 
 
@@ -155,7 +145,6 @@ class _SchurSolve:
 
     def __init__(self, ops, inner):
         self.ops, self.inner, self.n = ops, inner, ops.n
-        import inspect
         self._sweep_kw = "sweep" in inspect.signature(inner).parameters      # the iterative inner solver is told which solves are sweeps
         self.rhs = torch.empty(ops.N, dtype=CDT, device="cuda")
         self.q = torch.empty(ops.N, dtype=CDT, device="cuda")
@@ -254,7 +243,7 @@ class WEPGMRESLinSolver(LinSolver):
         # issued directly, without the copy in / copy out of a graph on fixed buffers (measured on C5: 1.29 s against 1.35 s);
         # the graph remains for the piecewise routes (~30 launches from Python per step)
         Pl = self.gmres._Pl_call
-        direct = self.ops.stencil is not None and isinstance(Pl, WEPPreconditioner) and Pl.fused_available()
+        direct = self.ops.stencil is not None and isinstance(Pl, WEPPreconditioner) and Pl._fused
         if Pl is not None and not direct:
             self._capture_step()
         elif direct:
@@ -360,49 +349,26 @@ class WEPPreconditioner:
         v = np.zeros(nz, dtype=complex); v[0] = -2; v[1] = 1; v[nz - 1] = 1; v /= wd.hz ** 2
         w = np.zeros(nz, dtype=complex); w[1] = 1; w[nz - 1] = -1; w *= self.sigma / wd.hz
         D = np.fft.fft(v + w) + (self.sigma ** 2 + k_bar)
-        # Sylvester solve: prime-factor DFT along z + one tridiagonal solve per z-mode along x (csrc/wep.hip); the dense
-        # transform matrices of round 1 (dense GEMMs, since round 3 the library's own k_gemm_general) serve the shapes those
-        # kernels do not take (nx > 2048)
-        self.sylv = None
+        # Sylvester solve: prime-factor DFT along z + one tridiagonal solve per z-mode along x (csrc/wep.hip); it takes every
+        # nx = nz + 4 <= 2048 (tests/test_host_wep_checkers.py), a larger grid is refused here
         self.dd1 = (2 / wd.hx) / wd.hx ** 2; self.dd2 = (-1 / (2 * wd.hx)) / wd.hx ** 2
         h = c_vp()
         Dc = np.ascontiguousarray(D, dtype=np.complex128)
-        st = lib.nep_wep_sylv_create(nz, nx, _lib.hptr(Dc), 1.0 / wd.hx ** 2, C.byref(h))
-        if st == 0:
-            self.sylv = h
-        elif st != _lib.NEP_ERR_UNSUPPORTED:
-            check(st)
-        if self.sylv is None:
-            S = -(4.0 / wd.hx ** 2) * np.sin(np.pi * np.arange(1, nx + 1) / (2 * (nx + 1))) ** 2
-            self.G = to_dev(1.0 / (D[:, None] + S[None, :]))                                   # nz x nx
-            self.Fs = to_dev(np.fft.fft(np.eye(nz), axis=0) / np.sqrt(nz))                     # unitary DFT, symmetric
-            jx = np.arange(1, nx + 1)
-            self.Wr = torch.from_numpy(np.ascontiguousarray(np.sqrt(2.0 / (nx + 1)) * np.sin(np.pi * np.outer(jx, jx) / (nx + 1)))).to("cuda")
+        check(lib.nep_wep_sylv_create(nz, nx, _lib.hptr(Dc), 1.0 / wd.hx ** 2, C.byref(h)))
+        self.sylv = h
         self.Ksc = to_dev(Kmat - k_bar)                                                    # K_scaled (Waveguide.jl:229-230)
-        # ---- regions: indicator matrices (z: nz x N; x: nx x (N+4)), kappa = i + N j
-        Bz = np.kron(np.eye(N), np.ones((L, 1)))
-        Bx = np.zeros((nx, N + 4))
-        Bx[0, 0] = Bx[1, 1] = Bx[nx - 2, N + 2] = Bx[nx - 1, N + 3] = 1.0
-        for j in range(N):
-            Bx[2 + j * L:2 + (j + 1) * L, 2 + j] = 1.0
-        wx = np.ones(N + 4); wx[2:N + 2] = 1.0 / L
-        self.Bz = to_dev(Bz); self.Bx = to_dev(Bx)
-        self.Az = to_dev(Bz.T / L)                                                         # N x nz: region means along z
-        self.Ax = to_dev(Bx * wx[None, :])                                                 # nx x (N+4): means along x
-        dd1 = (2 / wd.hx) / wd.hx ** 2; dd2 = (-1 / (2 * wd.hx)) / wd.hx ** 2
-        cb = np.zeros((N + 4, 2)); cb[0, 0] = dd1; cb[1, 0] = dd2; cb[N + 2, 1] = dd2; cb[N + 3, 1] = dd1
-        self.cb = to_dev(cb)
-        # ---- work space
-        e = lambda *shape: torch.empty(shape, dtype=CDT, device="cuda")
-        self.T1, self.T2, self.Y, self.Cw = e(nx, nz), e(nx, nz), e(nx, nz), e(nx, nz)
-        self.tz = e(N + 4, nz)                 # nz x (N+4)
-        self.fb = e(N + 4, N)                  # N x (N+4): functionals / alpha
-        self.al = e(N + 4, N)
-        self.eb = e(2, nz)                     # nz x 2 = [e_minus, e_plus]
-        self.pb = e(2 * nz)
+        # ---- work space of the piecewise route; regions: kappa = i + N j
+        self.Y = torch.empty((nx, nz), dtype=CDT, device="cuda")
+        self.fb = torch.empty((N + 4, N), dtype=CDT, device="cuda")        # N x (N+4): functionals
+        self.al = torch.empty((N + 4, N), dtype=CDT, device="cuda")        # alpha
+        self.eb = torch.empty((2, nz), dtype=CDT, device="cuda")           # nz x 2 = [e_minus, e_plus]
+        self.pb = torch.empty(2 * nz, dtype=CDT, device="cuda")
         self.MinvH = None
-        self._G = None
-        self._fused = False if env_str("NEP_WEP_SMW_FUSED", "1") == "0" else None     # None: not tried yet
+        # ---- the route, fixed here: nep_wep_plan evaluates the predicates nep_wep_smw_apply / nep_wep_smw_matrix_modes test
+        info = (C.c_int64 * 8)()
+        self._fused = (env_str("NEP_WEP_SMW_FUSED", "1") != "0" and nep._pinv_plan() is not None
+                       and lib.nep_wep_plan(nz, nx, PLAN_SMW, info) == _lib.NEP_OK)
+        self._G = self._mode_means_matrix() if self._fused else None
         self._generate()
 
     def __del__(self):
@@ -415,84 +381,59 @@ class WEPPreconditioner:
 
     # -- pieces
     def linv(self, X):
-        """in place Sylvester solve on a device nz x nx matrix (column-major): X <- F (G .* (F^H X W)) W; the two products
-        with the real W run as real GEMMs"""
-        nz, nx = self.nep.nz, self.nep.nx
-        if self.sylv is not None:
-            check(lib.nep_wep_sylv_solve(self.sylv, _p(X), stream_ptr()))
-            return X
-        self._xw(X, self.T1)
-        zgemm(C_, N_, nz, nx, nz, 1.0, self.Fs, nz, self.T1, nz, 0.0, self.T2, nz)
-        check(lib.nep_hadamard(nz * nx, 1, c_vp(self.T2.data_ptr()), nz * nx, c_vp(self.G.data_ptr()), nz * nx, stream_ptr()))
-        self._xw(self.T2, self.T1)
-        zgemm(N_, N_, nz, nx, nz, 1.0, self.Fs, nz, self.T1, nz, 0.0, X, nz)
+        """in place Sylvester solve on a device nz x nx matrix (column-major): prime-factor DFT along z, one tridiagonal solve
+        per z-mode along x, back transform"""
+        check(lib.nep_wep_sylv_solve(self.sylv, _p(X), stream_ptr()))
         return X
-
-    def _xw(self, X, out):
-        """out = X W for the real symmetric sine-transform matrix W: the complex nz x nx block as a real 2 nz x nx block"""
-        nz, nx = self.nep.nz, self.nep.nx
-        check(lib.nep_dgemm(0, 0, 2 * nz, nx, nx, 1.0, _p(X), 2 * nz, c_vp(self.Wr.data_ptr()), nx, 0.0, _p(out), 2 * nz,
-                            stream_ptr()))
 
     def functionals(self, X, out):
         """out (N x (N+4)) = region means of X (waveguide_preconditioner.jl:297-304)"""
-        nz, nx, N = self.nep.nz, self.nep.nx, self.N
-        if self.sylv is not None:
-            check(lib.nep_wep_region_means(nz, nx, N, _p(X), _p(out), stream_ptr()))
-            return out
-        zgemm(N_, N_, nz, N + 4, nx, 1.0, X, nz, self.Ax, nx, 0.0, self.tz, nz)
-        zgemm(N_, N_, N, N + 4, nz, 1.0, self.Az, N, self.tz, nz, 0.0, out, N)
+        check(lib.nep_wep_region_means(self.nep.nz, self.nep.nx, self.N, _p(X), _p(out), stream_ptr()))
         return out
 
     def expand(self, alpha, Y):
         """Y (nz x nx) = sum_k alpha_k E_k  (waveguide_preconditioner.jl:263-288, :382-412): K_scaled restricted to the regions,
         plus -P^{-1}(sigma) of the boundary pieces in the first and last column"""
         nz, nx, N = self.nep.nz, self.nep.nx, self.N
-        if self.sylv is not None:
-            check(lib.nep_wep_region_expand(nz, nx, N, _p(alpha), _p(self.Ksc), self.dd1, self.dd2, _p(Y), _p(self.eb), stream_ptr()))
-        else:
-            zgemm(N_, N_, nz, N + 4, N, 1.0, self.Bz, nz, alpha, N, 0.0, self.tz, nz)            # Bz A
-            zgemm(N_, T_, nz, nx, N + 4, 1.0, self.tz, nz, self.Bx, nx, 0.0, Y, nz)               # (Bz A) Bx^T
-            check(lib.nep_hadamard(nz * nx, 1, c_vp(Y.data_ptr()), nz * nx, c_vp(self.Ksc.data_ptr()), nz * nx, stream_ptr()))
-            zgemm(N_, N_, nz, 2, N + 4, 1.0, self.tz, nz, self.cb, N + 4, 0.0, self.eb, nz)       # [e_-, e_+]
+        check(lib.nep_wep_region_expand(nz, nx, N, _p(alpha), _p(self.Ksc), self.dd1, self.dd2, _p(Y), _p(self.eb), stream_ptr()))
         self.ops.pinv(self.eb, self.pb)
         dense.axpy(-1.0, self.pb, Y, nz)                                                     # column 1       -= P_-^{-1} e_-
-        check(lib.nep_axpy(nz, _lib.cd(-1.0), c_vp(self.pb.data_ptr() + 16 * nz), c_vp(Y.data_ptr() + 16 * nz * (nx - 1)),
-                           stream_ptr()))                                                    # column nx      -= P_+^{-1} e_+
+        check(lib.nep_axpy(nz, _lib.cd(-1.0), _p(self.pb, nz), _p(Y, nz * (nx - 1)), stream_ptr()))    # column nx -= P_+^{-1} e_+
         return Y
 
+    # -- the SMW matrix: one of three routes
     def _generate(self):
-        """waveguide_preconditioner.jl:221-313: M[:, k] = f(Linv E_k) + identity, inverted once (host, mm x mm)"""
-        N, mm = self.N, self.mm
-        Mdev = torch.empty((mm, mm), dtype=CDT, device="cuda")            # column kappa at Mdev[kappa]
-        plan = self.nep._pinv_plan()
-        if self.sylv is not None and plan is not None:
-            # all mm columns inside the library (one foreign call instead of ~8 per column)
-            nz, nx = self.nep.nz, self.nep.nx
-            st = _lib.NEP_ERR_UNSUPPORTED
-            if self._fused is not False:
-                # mode-space form (no back transforms, interior columns batched); falls through when the grid does not take it
-                if self._G is None:
-                    self._G = self._mode_means_matrix()
-                st = lib.nep_wep_smw_matrix_modes(self.sylv, plan, N, _p(self.Ksc), self.dd1, self.dd2, _p(self.ops.sinv), _p(self._G),
-                                                  _p(Mdev), stream_ptr())
-                if st not in (0, _lib.NEP_ERR_UNSUPPORTED):
-                    check(st)
-            if st != 0:
-                work = torch.empty(nz * nx + 4 * nz + mm, dtype=CDT, device="cuda")
-                check(lib.nep_wep_smw_matrix(self.sylv, plan, N, _p(self.Ksc), self.dd1, self.dd2, _p(self.ops.sinv), _p(work), _p(Mdev),
-                                             stream_ptr()))
-            self._set_inverse(Mdev, mm)
-            return
-        unit = torch.zeros((N + 4, N), dtype=CDT, device="cuda").reshape(-1)
+        """waveguide_preconditioner.jl:221-313: M[:, k] = f(Linv E_k) + identity, inverted once (mm x mm)"""
+        Mdev = torch.empty((self.mm, self.mm), dtype=CDT, device="cuda")            # column kappa at Mdev[kappa]
+        if self._fused:
+            self._matrix_modes(Mdev)
+        elif self.nep._pinv_plan() is not None:
+            self._matrix_library(Mdev)
+        else:
+            self._matrix_by_columns(Mdev)
+        self._set_inverse(Mdev, self.mm)
+
+    def _matrix_modes(self, Mdev):
+        """mode-space form (no back transforms, interior columns batched): the set-up of the three-transform form"""
+        check(lib.nep_wep_smw_matrix_modes(self.sylv, self.nep._pinv_plan(), self.N, _p(self.Ksc), self.dd1, self.dd2, _p(self.ops.sinv),
+                                           _p(self._G), _p(Mdev), stream_ptr()))
+
+    def _matrix_library(self, Mdev):
+        """all mm columns of the piecewise form inside the library (one foreign call instead of ~8 per column)"""
+        work = torch.empty(self.nep.nz * self.nep.nx + 4 * self.nep.nz + self.mm, dtype=CDT, device="cuda")
+        check(lib.nep_wep_smw_matrix(self.sylv, self.nep._pinv_plan(), self.N, _p(self.Ksc), self.dd1, self.dd2, _p(self.ops.sinv),
+                                     _p(work), _p(Mdev), stream_ptr()))
+
+    def _matrix_by_columns(self, Mdev):
+        """column by column through the pieces: the grids without a P^{-1} plan (nz >= 1921)"""
+        unit = torch.zeros((self.N + 4, self.N), dtype=CDT, device="cuda").reshape(-1)
         one = torch.ones(1, dtype=CDT, device="cuda")
-        for kappa in range(mm):
+        for kappa in range(self.mm):
             unit.zero_()
             unit[kappa:kappa + 1].copy_(one)
             self.expand(unit, self.Y)
             self.linv(self.Y)
             self.functionals(self.Y, Mdev[kappa])
-        self._set_inverse(Mdev, mm)
 
     def _set_inverse(self, Mdev, mm):
         """MinvH = inv(I + M)^H (alpha = (MinvH)^H f through nep_gemv_hd).  On the device by the library's Gauss-Jordan inverse
@@ -535,35 +476,25 @@ class WEPPreconditioner:
         G = outer * inner[None, :] / np.sqrt(nz)
         return to_dev(np.ascontiguousarray(G).T)                                       # to_dev stores (rows, cols) column-major
 
-    def fused_available(self):
-        """True when nep_wep_smw_apply takes this grid (tried once on a zero vector)"""
-        if self._fused is None:
-            self(torch.zeros(self.nep.nz * self.nep.nx, dtype=CDT, device="cuda"))
-        return self._fused is True
-
     def __call__(self, r):
         """solve_smw (waveguide_preconditioner.jl:323-421), in place on the device vector r"""
-        nz, nx, N, mm = self.nep.nz, self.nep.nx, self.N, self.mm
-        if self.sylv is not None and self._fused is not False:
-            plan = self.nep._pinv_plan()
-            if plan is not None:
-                if self._G is None:
-                    self._G = self._mode_means_matrix()
-                st = lib.nep_wep_smw_apply(self.sylv, plan, N, _p(self.Ksc), self.dd1, self.dd2, _p(self.ops.sinv), _p(self.MinvH),
-                                           _p(self._G), _p(r), stream_ptr())
-                if st == 0:
-                    self._fused = True
-                    return r
-                if st != _lib.NEP_ERR_UNSUPPORTED:
-                    check(st)
-            self._fused = False                                                # piecewise route from now on
+        return self._apply_fused(r) if self._fused else self._apply_piecewise(r)
+
+    def _apply_fused(self, r):
+        """three transforms, the region means and the second solve in mode space (one foreign call)"""
+        check(lib.nep_wep_smw_apply(self.sylv, self.nep._pinv_plan(), self.N, _p(self.Ksc), self.dd1, self.dd2, _p(self.ops.sinv),
+                                    _p(self.MinvH), _p(self._G), _p(r), stream_ptr()))
+        return r
+
+    def _apply_piecewise(self, r):
+        """as the reference writes it: four transforms"""
+        mm = self.mm
         self.linv(r)                                                           # C = Linv r
         self.functionals(r, self.fb)
-        check(lib.nep_gemv_hd(c_vp(self.MinvH.data_ptr()), mm, mm, mm, c_vp(self.fb.data_ptr()), None, c_vp(self.al.data_ptr()),
-                              stream_ptr()))
+        check(lib.nep_gemv_hd(_p(self.MinvH), mm, mm, mm, _p(self.fb), None, _p(self.al), stream_ptr()))
         self.expand(self.al, self.Y)
         self.linv(self.Y)
-        dense.axpy(-1.0, self.Y, r, nz * nx)
+        dense.axpy(-1.0, self.Y, r, self.nep.nz * self.nep.nx)
         return r
 
 

@@ -656,7 +656,7 @@ def test_zgemm_vs_numpy(na, ta, tb):
     """nep_zgemm (the library's own LDS-tiled GEMM behind the C ABI, csrc/gemm.hip k_gemm_general; no vendor BLAS): C = alpha op(A) op(B) + beta C with none / transpose / conjugate
     transpose, leading dimensions larger than the matrices; 1e-13 relative (k = 77 products per entry)"""
     import torch
-    from nep_amd.wep_linsolvers import zgemm
+    from nep_amd.dense import zgemm
     rng = np.random.default_rng(10 * ta + tb)
     m, n, k = 53, 41, 77
     op = lambda X, t: X if t == 0 else (X.T if t == 1 else X.conj().T)

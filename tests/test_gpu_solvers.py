@@ -1403,17 +1403,16 @@ def test_wep_preconditioner_three_transform_form(na, nz, N):
         P0 = na.wep_generate_preconditioner(nep, N, lam)
     finally:
         del os.environ["NEP_WEP_SMW_FUSED"]
+    assert P._fused is True, "the three-transform form was not taken"
     assert P0._fused is False and P._G is not None
     assert np.linalg.norm(P._M - P0._M) <= 1e-12 * np.linalg.norm(P0._M), np.linalg.norm(P._M - P0._M) / np.linalg.norm(P0._M)
     rng = np.random.default_rng(nz + N)
     v = rng.standard_normal(nx * nz) + 1j * rng.standard_normal(nx * nz)
     r1 = na.to_dev(v)[0].clone(); r2 = na.to_dev(v)[0].clone()
     P(r1)
-    assert P._fused is True, "the three-transform form was not taken"
-    P._fused = False
-    P(r2)
-    P._fused = None
+    P0(r2)                                                                     # the piecewise route, fixed at set-up
     torch.cuda.synchronize()
+    assert P._fused is True and P0._fused is False
     a = na.to_host(r1.reshape(1, -1))[:, 0]; b = na.to_host(r2.reshape(1, -1))[:, 0]
     assert np.linalg.norm(a - b) <= 1e-12 * np.linalg.norm(b), np.linalg.norm(a - b) / np.linalg.norm(b)
     r3 = na.to_dev(v)[0].clone()
@@ -1425,6 +1424,7 @@ def test_wep_preconditioner_three_transform_form(na, nz, N):
         ops.matvec(na.to_dev(v)[0], out)
         w = P(out); torch.cuda.synchronize()
         assert np.linalg.norm(na.to_host(w.reshape(1, -1))[:, 0] - v) <= 1e-11 * np.linalg.norm(v)
+    assert P._fused is True and P0._fused is False
 
 
 @pytest.mark.parametrize("nz,nx", [(7, 11), (105, 109), (299, 303), (60, 64), (111, 115), (999, 1003)])

@@ -170,6 +170,15 @@ def test_plan_equals_the_restated_predicates():
     print("plans compared: %d" % n)
 
 
+def test_sylvester_plan_takes_every_grid_the_preconditioner_admits():
+    """WEPPreconditioner insists on nx = nz + 4 and a WEP on odd nz: for every such grid up to nx = 2048 the Sylvester solve has a
+    plan, and nx = 2049 is refused as an argument error -- so nep_wep_sylv_create never answers "unsupported" to the preconditioner,
+    which therefore keeps no dense-transform route"""
+    for nz in range(1, 2045, 2):
+        assert _plan(nz, nz + 4, wc.OP_SYLV)[0] == 0, nz
+    assert _plan(2045, 2049, wc.OP_SYLV) == (-2, [0] * 8)
+
+
 def test_zz_report():
     total = sum(len(k.mutants) for k in wc.CHECKERS.values())
     print("calls passed by the restatement: %d; mutants rejected: %d of %d" % (PASSED[0], len(REJECTED), total))
