@@ -898,6 +898,40 @@ int32_t nep_allgather_sum(nep_comm* c, const nep_cdouble* d_partial, int64_t len
  * d_total may alias block 0.  For tests and for hosts that move the blocks themselves. */
 int32_t nep_sum_ranks(const nep_cdouble* d_parts, int64_t len, int32_t world, nep_cdouble* d_total, nep_stream stream);
 
+/* ---- boundary-element NEP (gallery "bem_fichera"): a dense M(lam) assembled on the device -------------------------------
+ * replaces: src/gallery_extra/bem_hardcoded/ -- precompute_quad! and assemble_BEM (assemble_BEM.jl:4-89: an n^2 scalar loop that
+ *           allocates per entry), deHoop (deHoop.jl:30-65), the auxiliary mesh data of genmesh.jl:95-111, and the
+ *           compute_Mlincomb_from_Mder delegation of bem_hardcoded.jl:36 (one assembled matrix per derivative).
+ * With the 3-point Gauss rule (points g_r[i], weights w_r[i] = area_r / 3), W_p = w_r[i] w_c[j], d_p = |g_r[i] - g_c[j]|, p = (i, j):
+ *   M(lam)[r, c]     = sum_p W_p (exp(i lam d_p) - 1) / d_p / (4 pi) + S0[r, c],        r <= c,
+ *   M^(m)(lam)[r, c] = sum_p W_p (i d_p)^m exp(i lam d_p) / d_p / (4 pi),   m >= 1;
+ * a pair with d_p == 0 contributes i lam W_p (m = 0), i W_p (m = 1), 0 (m >= 2) inside the sum; the lower triangle is the
+ * mirror of the upper one.  S0: the Gauss rule over triangle r of de Hoop's closed form for triangle c, / (4 pi), with |R| + R.tau
+ * evaluated as h^2 / (|R| - R.tau) where R.tau < 0 (no cancellation).
+ * nep_bem_create: h_vert = n x 9 doubles (P1, P2, P3 of each triangle), h_area = n doubles; uploads the mesh, derives Gauss
+ *   points, tangents, normal and edge normals and fills S0 on the device; synchronous.  NEP_ERR_UNSUPPORTED: gauss_order != 3.
+ * nep_bem_info: info = (n, gauss_order, device bytes, coefficients per pass of nep_bem_mlincomb).
+ * nep_bem_static: d_out (n x n doubles, column-major, ldo >= n) = S0 (mirrored).
+ * nep_bem_assemble: dOut + l stride = M^(der)(h_lam[l]), l < nlam, column-major n x n (ldo >= n); the 9 distances of an entry
+ *   are formed once for the whole batch; the output is bitwise symmetric; nlam = 0 is a no-op.
+ * nep_bem_mlincomb: dz = sum_{j < k} h_a[j] M^(j + startder)(lam) dV[:, j], matrix-free: one pass over the pairs with a Horner
+ *   loop in (i d_p), no n^2 buffer except the read of S0; k > 64 in passes of 64.  h_a[j] == 0 drops column j (never read).
+ * nep_bem_resid: dOut[:, s] = M(h_lam[s]) dQ[:, s], s < k, matrix-free (dQ, dOut column-major, ldq, ldo >= n).
+ * All but create are asynchronous; host arrays may be freed on return (they travel as kernel arguments).  Padding (rows >= n of
+ * a column, columns beyond n) is never written.  No atomics, fixed summation order: two calls give the same bits.
+ * NEP_ERR_ARG (nothing launched) for a NULL handle or block, a leading dimension < n, k < 1, nlam < 0, der < 0, startder < 0. */
+typedef struct nep_bem nep_bem;
+int32_t nep_bem_create(int64_t n, const double* h_vert, const double* h_area, int32_t gauss_order, nep_bem** out);
+int32_t nep_bem_destroy(nep_bem* b);
+int32_t nep_bem_info(const nep_bem* b, int64_t info[4]);
+int32_t nep_bem_static(const nep_bem* b, double* d_out, int64_t ldo, nep_stream stream);
+int32_t nep_bem_assemble(const nep_bem* b, int32_t nlam, const nep_cdouble* h_lam, int32_t der, nep_cdouble* dOut, int64_t ldo,
+                         int64_t stride, nep_stream stream);
+int32_t nep_bem_mlincomb(const nep_bem* b, nep_cdouble lam, int32_t k, const nep_cdouble* h_a, int32_t startder,
+                         const nep_cdouble* dV, int64_t ldv, nep_cdouble* dz, nep_stream stream);
+int32_t nep_bem_resid(const nep_bem* b, int32_t k, const nep_cdouble* h_lam, const nep_cdouble* dQ, int64_t ldq, nep_cdouble* dOut,
+                      int64_t ldo, nep_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

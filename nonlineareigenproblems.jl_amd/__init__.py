@@ -48,3 +48,4 @@ from . import wep_linsolvers
 from .wep_linsolvers import (WEPLinSolverCreator, WEPFactorizedLinSolver, WEPBackslashLinSolver, WEPGMRESLinSolver,
                              wep_generate_preconditioner, construct_WEP_schur_complement)
 from .gallery import nep_gallery
+from .bem import BEM_NEP, TriMesh, gen_ficheramesh

@@ -106,6 +106,13 @@ SIGNATURES = {
     "nep_defl_border": [c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp],
     "nep_cork_expand": [c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, cdouble, c_vp, c_i64, c_vp],
     "nep_interp_coeffs": [c_i64, c_i32, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp],
+    "nep_bem_create": [c_i64, c_vp, c_vp, c_i32, P(c_vp)],
+    "nep_bem_destroy": [c_vp],
+    "nep_bem_info": [c_vp, P(c_i64)],
+    "nep_bem_static": [c_vp, c_vp, c_i64, c_vp],
+    "nep_bem_assemble": [c_vp, c_i32, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp],
+    "nep_bem_mlincomb": [c_vp, cdouble, c_i32, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp],
+    "nep_bem_resid": [c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
     "nep_broyden_sweep_worksize": [c_i64],
     "nep_broyden_sweep": [c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "nep_resid_batch": [c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],

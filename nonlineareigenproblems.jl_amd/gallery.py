@@ -374,6 +374,16 @@ def particle_init(interval):
     return nep, np.array([xmin + 0j, xmax + 0j]), Xi, v, nodes, xmin, xmax
 
 
+def bem_fichera(N=3):
+    """src/gallery_extra/bem_hardcoded/bem_hardcoded.jl:40-45: boundary-element discretisation of the Laplace eigenvalue problem
+    on the unit cube with a Fichera corner, 24 N^2 triangles (N rounded up to even); M(lam) is assembled on the device"""
+    from .bem import BEM_NEP, gen_ficheramesh
+    return BEM_NEP(gen_ficheramesh(N))
+
+
+GALLERY["bem_fichera"] = bem_fichera
+
+
 def nep_gallery(name, *args, **kwargs):
     if name not in GALLERY:
         raise KeyError("unknown gallery problem %r (available: %s)" % (name, ", ".join(sorted(GALLERY))))

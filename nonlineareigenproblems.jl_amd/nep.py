@@ -777,6 +777,7 @@ class PEP(AbstractSPMF):
 
 # ---- interpolation of a NEP: ChebPEP (src/types_cheb_pep.jl) and interpolate (src/types_poly.jl:101-167) -----------------------
 INTERP_MAX = 64                      # nep_interp_coeffs: 1 <= J, K <= 64
+INTERP_SAMPLE_WORDS = 1 << 28        # device samples of a dense NEP held at a time by _interp_on_device (4 GiB)
 
 
 def chebyshev_nodes(a, b, k):
@@ -837,6 +838,7 @@ def _interp_on_device(orgnep, points, W, table=True):
 
     table route (a pure sparse SPMF with at most 64 terms whose aligned term block exists): M(x_j) = sum_t f_t(x_j) A_t, so the
     coefficients are (W [f_t(x_j)]) applied to the term block D that is already on the device; no matrix is assembled.
+    device-sample route (a type that offers compute_Mder_dev: BEM_NEP): the dense samples are assembled on the device and stay there.
     sampling route (anything else): compute_Mder at every point on the host, one upload and one call per sample."""
     _lib.require_gpu()
     W = np.atleast_2d(np.asarray(W))
@@ -849,6 +851,19 @@ def _interp_on_device(orgnep, points, W, table=True):
         Cd = interp_coeffs(Dd, W @ Fx)
         real = bool(orgnep.is_real() and not np.iscomplexobj(points) and not np.iscomplexobj(W))
         sparse = True
+    elif hasattr(orgnep, "compute_Mder_dev"):
+        # a dense NEP that assembles on the device (BEM_NEP): the samples never visit the host.  Same calls, same order of the
+        # sums as the dense branch below; block [j] is M(points[j]) row-major, n^2 complex values.  The samples are assembled in
+        # chunks of at most INTERP_SAMPLE_WORDS complex words (all nodes at once up to n = 3600 with 20 nodes), so the peak is
+        # that chunk beside the n^2 K coefficient block, not J matrices
+        sparse, real = False, False
+        Cd = torch.empty((n * n, K), dtype=CDT, device="cuda")
+        step = max(1, INTERP_SAMPLE_WORDS // (n * n))
+        for j0 in range(0, len(points), step):
+            S = orgnep.compute_Mder_dev(points[j0:j0 + step])
+            for j in range(j0, j0 + S.shape[0]):
+                interp_coeffs(S[j - j0].reshape(-1, 1), W[:, j:j + 1], Cd, None, beta=int(j > 0))
+            del S
     else:
         samples = [orgnep.compute_Mder(x) for x in points]
         sparse = all(sp.issparse(S) for S in samples)
