@@ -363,7 +363,8 @@ __global__ __launch_bounds__(128) void k_hess_qr(int k0, int kstep, const cplx* 
         for (int r = lane; r <= rl; r += 64) {
             const cplx v = H[(size_t)c * ldh + r];
             A[hq_off(c) + r] = v;
-            amax = fmax(amax, fmax(fabs(v.x), fabs(v.y)));
+            const double av = fmax(fabs(v.x), fabs(v.y));               // fmax drops a NaN operand: a NaN entry counts as Inf
+            amax = (v.x != v.x || v.y != v.y) ? INFINITY : fmax(amax, av);
         }
     }
     // row-major copy for the eigenvector kernel (coalesced reads with lane = column there) and the infinity norm (zlanhs 'I')
