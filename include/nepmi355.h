@@ -932,6 +932,39 @@ int32_t nep_bem_mlincomb(const nep_bem* b, nep_cdouble lam, int32_t k, const nep
 int32_t nep_bem_resid(const nep_bem* b, int32_t k, const nep_cdouble* h_lam, const nep_cdouble* dQ, int64_t ldq, nep_cdouble* dOut,
                       int64_t ldo, nep_stream stream);
 
+/* ---- time-periodic delay NEP (gallery "periodicdde"): M(lam) by a Runge-Kutta sweep on the device (K15) -----------------
+ * replaces: src/gallery_extra/periodic_dde.jl -- ode_rk4 (:112-124) inside compute_MM (:203-218), the column-by-column
+ *           compute_Mder (:247-259) and its central differences for the first derivative (:260-265).
+ * x'(t) = A(t) x(t) + B(t) x(t - tau), A(t) = sum_{i < mA} alpha_i(t) A_i, B(t) = sum_{j < mB} beta_j(t) B_j, both tau-periodic.
+ *   MM(S, V) = Y_N - V,   Y_0 = V (n x p),   Y_{k+1} = Y_k + (s1 + 2 s2 + 2 s3 + s4) / 6,   s_i = h F(.), h = tau / N,
+ *   F(t, Y) = (sum_i alpha_i(t) A_i) Y + ((sum_j beta_j(t) B_j) Y) E - Y S,
+ * the classical Runge-Kutta stages at t_k, t_k + h/2, t_k + h/2, t_k + h.  With E = exp(-tau S) this is the reference's
+ * compute_MM; E is an input of its own and is not checked against S.
+ * nep_pdde_create: h_A = mA matrices, h_B = mB matrices, each n x n column-major, one after the other; h_alpha ((2N + 1) x mA,
+ *   row-major) and h_beta ((2N + 1) x mB) hold alpha_i and beta_j at the half-step times s tau / (2N): step k reads rows 2k, 2k+1,
+ *   2k+1, 2k+2.  1 <= n <= 512, 1 <= mA, mB <= 64, N >= 1.  Synchronous.
+ * nep_pdde_info: info = (n, N, device bytes, largest p).
+ * nep_pdde_mm: nsys systems of p <= 8 columns in ONE launch; system s has S = h_S + s p p and E = h_E + s p p (p x p,
+ *   column-major, host), V = dV + s strideV (n x p, ldv >= n, device, not modified) and writes MM(S, V) to dOut + s strideO (ldo >= n).
+ * nep_pdde_mder: dOut + l stride = M^(der)(h_lam[l]) (n x n, column-major, ldo >= n), l < nlam, der <= 7: a front end of the same
+ *   launch with S = J_{der+1}(lam) (ones above the diagonal), E = e^(-tau lam) Toeplitz((-tau)^k / k!) formed on the host in closed
+ *   form and V = [e_j, 0, ..., 0] generated on the device; column j of the matrix is der! times column der of system (l, j).
+ * mm and mder are asynchronous; host arrays may be freed on return.  Nothing outside the n x p blocks (mder: the n x n matrices)
+ * is written.  The sum over the inner index runs in a fixed order that belongs to the row and column alone: a system has the same
+ * bits alone, at any position of any batch, and from run to run.  nsys = 0 and nlam = 0 are no-ops.
+ * NEP_ERR_ARG (nothing launched) for a NULL handle or block, n outside 1..512, mA or mB outside 1..64, N outside 1..2^24, a tau
+ * that is not finite, p outside 1..8, der outside 0..7, a leading dimension < n, a stride smaller than a block (nsys, nlam > 1),
+ * nlam n > 2^31 - 1. */
+typedef struct nep_pdde nep_pdde;
+int32_t nep_pdde_create(int32_t n, int32_t mA, int32_t mB, const nep_cdouble* h_A, const nep_cdouble* h_B, int32_t N, double tau,
+                        const nep_cdouble* h_alpha, const nep_cdouble* h_beta, nep_pdde** out);
+int32_t nep_pdde_destroy(nep_pdde* d);
+int32_t nep_pdde_info(const nep_pdde* d, int64_t info[4]);
+int32_t nep_pdde_mm(const nep_pdde* d, int32_t nsys, int32_t p, const nep_cdouble* h_S, const nep_cdouble* h_E, const nep_cdouble* dV,
+                    int64_t ldv, int64_t strideV, nep_cdouble* dOut, int64_t ldo, int64_t strideO, nep_stream stream);
+int32_t nep_pdde_mder(const nep_pdde* d, int32_t nlam, const nep_cdouble* h_lam, int32_t der, nep_cdouble* dOut, int64_t ldo,
+                      int64_t stride, nep_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,7 @@ from .iar_chebyshev import iar_chebyshev
 from .ilan import ilan
 from .nlar import nlar, residual_eigval_sorter, default_eigval_sorter
 from .jd import jd_betcke, jd_effenberger, jd_eig_sorter
-from .newton import resinv, quasinewton, augnewton, compute_rf, armijo_rule, ScalarNewtonInnerSolver
+from .newton import newton, resinv, quasinewton, augnewton, compute_rf, armijo_rule, ScalarNewtonInnerSolver
 from .twosided import rfi, transpose_relation, twosided_linsolvers
 from .infbilanczos import infbilanczos, left_right_scalar_prod
 from .deflation import (deflate_eigpair, get_deflated_eigpairs, normalize_schur_pair, verify_deflate_mode, DeflatedNEPMM,
@@ -49,3 +49,4 @@ from .wep_linsolvers import (WEPLinSolverCreator, WEPFactorizedLinSolver, WEPBac
                              wep_generate_preconditioner, construct_WEP_schur_complement)
 from .gallery import nep_gallery
 from .bem import BEM_NEP, TriMesh, gen_ficheramesh
+from .pdde import PeriodicDDE_NEP

@@ -113,6 +113,11 @@ SIGNATURES = {
     "nep_bem_assemble": [c_vp, c_i32, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp],
     "nep_bem_mlincomb": [c_vp, cdouble, c_i32, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp],
     "nep_bem_resid": [c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
+    "nep_pdde_create": [c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_dbl, c_vp, c_vp, P(c_vp)],
+    "nep_pdde_destroy": [c_vp],
+    "nep_pdde_info": [c_vp, P(c_i64)],
+    "nep_pdde_mm": [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp],
+    "nep_pdde_mder": [c_vp, c_i32, c_vp, c_i32, c_vp, c_i64, c_i64, c_vp],
     "nep_broyden_sweep_worksize": [c_i64],
     "nep_broyden_sweep": [c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "nep_resid_batch": [c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libnepmi355.so")
 SOURCES = ["util.hip", "spmv.hip", "spmv_tile.hip", "orth.hip", "gemm.hip", "trsv.hip", "trsv_ml.hip", "comm.hip", "driver.hip", "wep.hip", "lufac.hip", "hesseig.hip", "iar_run.hip", "lrprod.hip", "deflate.hip",
-           "deflate_border.hip", "cork.hip", "broyden.hip", "blockprod.hip", "lineig.hip", "interp.hip", "biforms.hip", "bem.hip"]
+           "deflate_border.hip", "cork.hip", "broyden.hip", "blockprod.hip", "lineig.hip", "interp.hip", "biforms.hip", "bem.hip", "pdde.hip"]
 
 
 def _torch_lib_dir():

@@ -255,6 +255,30 @@ class _BeynTrace:
                                                       self._ms()), flush=True)
 
 
+class _BatchedMder:
+    """the NEP as the node solvers see it once the matrices of all nodes have come from ONE compute_Mder_batch call (a NEP type that
+    evaluates M on the device for a batch of shifts: PeriodicDDE_NEP, BEM_NEP): compute_Mder(lam) of a node hands out its matrix,
+    everything else is the NEP's own"""
+
+    BATCH_WORDS = 1 << 26      # complex words of one batch (1 GiB): more nodes than that take several calls
+
+    def __init__(self, nep, shifts):
+        self._nep = nep
+        n = nep.size(1)
+        step = max(1, self.BATCH_WORDS // (n * n))
+        self._mats = {}
+        for j0 in range(0, len(shifts), step):
+            part = [complex(z) for z in shifts[j0:j0 + step]]
+            self._mats.update(zip(part, nep.compute_Mder_batch(part)))
+
+    def __getattr__(self, name):
+        return getattr(self._nep, name)
+
+    def compute_Mder(self, lam, i=0):
+        M = self._mats.pop(complex(lam), None) if i == 0 else None       # (each node is factorised once)
+        return self._nep.compute_Mder(lam, i) if M is None else M
+
+
 class _NodeSolve:
     """f(t) = Tv(g(t)) * weight(t), Tv(lam) = lin_solve(create_linsolver(creator, nep, lam+sigma), Vh)
     (method_beyncontour.jl:89-98, method_block_SS.jl:81-86,129-132).  With the default BackslashLinSolverCreator every
@@ -300,6 +324,9 @@ class _NodeSolve:
     def prefetch(self, ts):
         """device batch, cold first node, or host pool: where the nodes ts are factorised"""
         c = self.creator
+        if (not isinstance(self.nep, _BatchedMder) and hasattr(self.nep, "compute_Mder_dev") and hasattr(self.nep, "compute_Mder_batch")
+                and len(ts) >= 1):
+            self.nep = _BatchedMder(self.nep, [self.g(t) + self.sigma for t in ts])      # M of every node from one device pass
         if not isinstance(c, BackslashLinSolverCreator) or getattr(c, "workers", None) == 0 or len(ts) < 2:
             return
         self.pool = ThreadPoolExecutor(max_workers=self.BUILDERS)

@@ -295,6 +295,11 @@ class NEP:
     def size(self, d=None):
         return (self.n, self.n) if d is None else self.n
 
+    def compute_resnorm(self, lam, v):
+        """||M(lam) v|| / ||v||  (NEPCore.jl compute_resnorm)"""
+        v = np.asarray(v, dtype=np.complex128)
+        return float(np.linalg.norm(self.compute_Mlincomb(lam, v)) / np.linalg.norm(v))
+
     # ---- the reference's generic fallbacks (src/NEPCore.jl:218-270) for NEP types that implement only ONE of the three compute
     # functions: a user type assigns e.g. `compute_Mlincomb = NEP.compute_Mlincomb_from_MM`, exactly as the reference's
     # `compute_Mlincomb(nep::MyNEP, lam, V, a) = compute_Mlincomb_from_MM(nep, lam, V, a)`.  The work is done by the type's own

@@ -1,6 +1,6 @@
-"""resinv, quasinewton, compute_rf (ScalarNewtonInnerSolver), armijo_rule on the device backend.
+"""newton, resinv, quasinewton, compute_rf (ScalarNewtonInnerSolver), armijo_rule on the device backend.
 
-Mirrors src/method_newton.jl:142-226 (resinv), :380-445 (quasinewton), :598-609 (armijo_rule) and
+Mirrors src/method_newton.jl:46-107 (newton), :142-226 (resinv), :380-445 (quasinewton), :598-609 (armijo_rule) and
 src/compute_rf_wrapper.jl:25-54 (compute_rf).  The eigenvector iterate lives on the device; per
 iteration only scalars (lambda, error, two dot products) cross PCIe.
 """
@@ -164,6 +164,54 @@ def armijo_rule(nep, errmeasure, err0, lam, v, dlam, dv, armijo_factor, armijo_m
             dense.scal(dv, armijo_factor)
             dlam = dlam * armijo_factor
     return dlam, dv, j, armijo_factor ** j
+
+
+def newton(nep, errmeasure=None, tol=EPS * 100, maxit=10, lam=0.0, v=None, c=None, logger=0, armijo_factor=1, armijo_max=5):
+    """Newton's method on the bordered system (method_newton.jl:46-107): J = [M(lam) M'(lam) v; c^H 0], F = [M(lam) v; c^H v - 1],
+    delta = -J \\ F, then the Armijo rule, then v += dv and lam += dlam, in the reference's order.  M(lam) comes from the NEP's
+    compute_Mder and the two products from its compute_Mlincomb (on the device); the (n + 1) x (n + 1) solve is the reference's
+    hard-coded backslash: LAPACK for a dense M, a sparse LU for a sparse one.  Works on every NEP type that has a host
+    compute_Mder(lam) (as the reference's newton needs): SPMF types, BEM_NEP, PeriodicDDE_NEP; not on a matrix-free type such as the
+    waveguide problem, which augnewton handles through its own linear solvers."""
+    import scipy.sparse as sp
+    import scipy.sparse.linalg as spla
+    n = nep.size(1)
+    lam = complex(lam)
+    if v is None:
+        v = np.random.randn(n)
+    vh = np.asarray(v, dtype=np.complex128).copy()
+    ch = vh.copy() if c is None else np.asarray(c, dtype=np.complex128).copy()
+    if errmeasure is None:
+        errmeasure = DefaultErrmeasure(nep)
+    vh = vh / np.vdot(ch, vh)
+    vd = to_dev(vh)[0]
+    err = np.inf
+    z = torch.empty((2, n), dtype=CDT, device="cuda")       # M(lam) v, M'(lam) v
+    for k in range(1, maxit + 1):
+        err = estimate_error(errmeasure, lam, vd)
+        if err < tol:
+            return lam, to_host(vd.reshape(1, n))[:, 0]
+        M = nep.compute_Mder(lam)
+        _mder_times(nep, lam, vd.reshape(1, n), z[0], 0)
+        _mder_times(nep, lam, vd.reshape(1, n), z[1], 1)
+        zh = to_host(z)                                       # n x 2
+        vh = to_host(vd.reshape(1, n))[:, 0]
+        F = np.concatenate([zh[:, 0], [np.vdot(ch, vh) - 1.0]])
+        if sp.issparse(M):
+            J = sp.bmat([[M, sp.csc_matrix(zh[:, 1].reshape(-1, 1))], [sp.csc_matrix(ch.conj().reshape(1, -1)), None]], format="csc",
+                        dtype=np.complex128)
+            delta = -spla.spsolve(J, F)
+        else:
+            J = np.zeros((n + 1, n + 1), dtype=np.complex128)
+            J[:n, :n] = M; J[:n, n] = zh[:, 1]; J[n, :n] = ch.conj()
+            delta = -np.linalg.solve(J, F)
+        dv = to_dev(delta[:n])[0]
+        dlam = complex(delta[n])
+        dlam, dv, j, scaling = armijo_rule(nep, errmeasure, err, lam, vd, dlam, dv, float(armijo_factor), armijo_max)
+        dense.axpy(1.0, dv, vd)
+        lam += dlam
+    raise NoConvergenceException(lam, to_host(vd.reshape(1, n))[:, 0], err,
+                                 "Number of iterations exceeded. maxit=%d." % maxit)
 
 
 def resinv(nep, errmeasure=None, tol=EPS * 100, maxit=100, lam=0.0, v=None, c=None, logger=0,
