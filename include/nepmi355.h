@@ -784,6 +784,14 @@ int32_t nep_iar_wait(nep_iar* s, int32_t k);
 /* device-side counterpart of nep_iar_wait: work enqueued on `stream` after this call starts only when column k of H is
  * complete (the eigen-decomposition of step k on a second stream: nep_hess_eigvals_dev on row block dH of nep_iar_create) */
 int32_t nep_iar_stream_wait(nep_iar* s, int32_t k, nep_stream stream);
+/* nep_iar_wait without the wait: *ready = 1 when column k of H has reached the pinned block, 0 while it has not */
+int32_t nep_iar_ready(nep_iar* s, int32_t k, int32_t* ready);
+/* Events only where something waits.  By default every step records an event (one more command on the stream per step); a
+ * caller that knows which steps it will pass to nep_iar_wait / nep_iar_ready / nep_iar_stream_wait names them: mask holds m + 1
+ * bytes indexed by the step (entry 0 unused, copied), step k records its event iff mask[k] != 0.  The three calls above return
+ * NEP_ERR_ARG for a step that recorded none.  NULL: every step records.  To be called before the first step of the object:
+ * NEP_ERR_ARG once a step has been issued. */
+int32_t nep_iar_event_mask(nep_iar* s, const uint8_t* mask);
 
 /* ---- a shift-and-invert Krylov-Schur eigensolver for a linear pencil A x = d B x (csrc/lineig.hip) ------------------------
  * K13  in-place basis rotation, the compression step of a Krylov-Schur restart:
@@ -843,7 +851,16 @@ int32_t nep_arnoldi_wait(nep_arnoldi* s, int32_t j);
  * pinned memory gets the link's rate), h_err (maxit x maxit column-major, err[k-1 + (s-1) maxit] = sorted error s of step k, NaN
  * where unset; may be NULL), dV_basis (device, maxit+1 columns of leading dimension n (maxit+1): the Krylov basis the reference
  * returns as V[:,1:k]; NULL: library-owned and released at return).  NEP_OK: res->nret converged pairs (all pairs below tol when neigs = INFINITY); NEP_ERR_NOCONV: the
- * res->nret best pairs; NEP_ERR_RETRY / NEP_ERR_UNSUPPORTED (maxit > 128): nothing returned, use the per-step entry points. */
+ * res->nret best pairs; NEP_ERR_RETRY / NEP_ERR_UNSUPPORTED (maxit > 128): nothing returned, use the per-step entry points.
+ * h_err == NULL says that nobody reads the error history.  With neigs = INFINITY the stop test cannot fire and everything the
+ * call returns comes from the check of step maxit, so then ONLY that step is checked: one eigen-decomposition, one Ritz block,
+ * one residual batch, one fv callback, whatever check_error_every says; h_lam, dQ / h_Q, dV_basis and res are bit for bit what
+ * the call with a buffer returns.  With a finite neigs every check step is checked, buffer or not (the stop test needs them).
+ * The recorded rows of H (breakdown, a wanted DGKS pass, the refinement record) are reviewed from the recurrence's loop at a
+ * fixed distance behind the steps being enqueued, checks or no checks: a miss is reported when its row has arrived, and the
+ * refinement sweeps every step takes do not depend on h_err.
+ * nep_iar_run_stats: what the last run of the calling thread launched -- out[0] eigen-decompositions, out[1] checks (Ritz block
+ * + residual batch + callback), out[2] step events recorded, out[3] rows of H reviewed. */
 typedef struct nep_iar_opts {
     int32_t maxit;               /* m */
     int32_t check_error_every;
@@ -875,6 +892,7 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
                     const nep_cdouble* h_Ctab, int32_t mt, const double* h_cabs, const nep_cdouble* h_cf, const double* h_fro,
                     nep_fv_eval fv, void* ctx, nep_cdouble* h_lam, nep_cdouble* dQ, nep_cdouble* h_Q, double* h_err,
                     nep_cdouble* dV_basis, nep_iar_result* res, nep_stream stream);
+int32_t nep_iar_run_stats(int32_t out[4]);
 
 /* ---- multi-GPU exchange of the contour integrators ----------------------------------------
  * replaces: the reduction inside `integrate_interval(::Type{<:MatrixIntegrator}, ...)` src/method_contour_common.jl:46,61-94

@@ -186,6 +186,8 @@ SIGNATURES = {
     "nep_iar_steps": [c_vp, c_i32, c_i32, c_i32, c_vp],
     "nep_iar_wait": [c_vp, c_i32],
     "nep_iar_stream_wait": [c_vp, c_i32, c_vp],
+    "nep_iar_ready": [c_vp, c_i32, P(c_i32)],
+    "nep_iar_event_mask": [c_vp, c_vp],
     "nep_basis_rotate": [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_i64, c_i32, c_vp],
     "nep_arnoldi_create": [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, P(c_vp)],
     "nep_arnoldi_destroy": [c_vp],
@@ -195,6 +197,7 @@ SIGNATURES = {
     "nep_devprim_sort_pairs": [c_vp, c_vp, c_i64, c_i32, c_vp],
     "nep_refine_review": [c_i32, c_i32, c_i32, c_vp, c_i32, c_vp],
     "nep_iar_run": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "nep_iar_run_stats": [P(c_i32)],
     "nep_hess_eig_worksize": [c_i32, P(c_i64)],
     "nep_hess_eigvals_dev": [c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp],
     "nep_hess_eigvecs_dev": [c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],

@@ -33,6 +33,8 @@ struct nep_iar {
     hipEvent_t e_upload = nullptr; bool upload_waited = false;      // |f_t|, f_t were uploaded on the NULL stream
     hipStream_t last = nullptr;
     bool no_events = false;                  // nep_iar_steps_graph: the steps are being captured, their events are recorded behind the graph launch
+    std::vector<uint8_t> ev_mask;            // nep_iar_event_mask: ev_mask[k] != 0 -- step k records its event (empty: every step does)
+    int32_t n_ev = 0;                        // events recorded so far
     std::vector<hipGraphExec_t> graphs;      // chunk graphs launched so far (destroyed with the object: a graph must outlive its execution)
     // step k's last kernel (k_orth_finish_vc) forms step k + 1's coefficient product and block shift: dWT (n x mt) holds the
     // product for step `wt_for` (0: none)
@@ -166,9 +168,29 @@ int32_t nep_iar_step(nep_iar* s, int32_t k, int32_t refine_steps, nep_stream str
     if (rc) return rc;
     if (!mirror)
         HIPCHK(hipMemcpyAsync(s->hH + (int64_t)(k - 1) * (s->m + 4), hrow, (size_t)(k + 4) * sizeof(cplx), hipMemcpyDeviceToHost, st));
-    if (s->no_events) return NEP_OK;
+    if (s->no_events || (!s->ev_mask.empty() && !s->ev_mask[k])) return NEP_OK;
     if (!s->ev[k]) HIPCHK(hipEventCreateWithFlags(&s->ev[k], hipEventDisableTiming | hipEventBlockingSync));
     HIPCHK(hipEventRecord(s->ev[k], st));
+    ++s->n_ev;
+    return NEP_OK;
+}
+
+// An event record is a command of its own on the stream (a gap at every step edge of the trace): a caller that knows which
+// steps anybody will wait for (nep_iar_wait / nep_iar_ready / nep_iar_stream_wait) names them, the other steps record nothing.
+// mask: m + 1 bytes indexed by the step (entry 0 unused), copied; NULL: every step records its event again.
+// Set before the first step only: a change between steps would leave events of earlier steps behind that the waits could
+// not tell from recorded ones.
+int32_t nep_iar_event_mask(nep_iar* s, const uint8_t* mask) {
+    ARGCHK(s != nullptr);
+    ARGCHK(s->last == nullptr && s->n_ev == 0);
+    if (mask) s->ev_mask.assign(mask, mask + s->m + 1); else s->ev_mask.clear();
+    return NEP_OK;
+}
+
+// internal (exported for csrc/iar_run.hip only, not part of the header): events recorded so far, for nep_iar_run_stats
+int32_t nep_iar_events_recorded(const nep_iar* s, int32_t* out) {
+    ARGCHK(s && out);
+    *out = s->n_ev;
     return NEP_OK;
 }
 
@@ -217,8 +239,10 @@ int32_t nep_iar_steps_graph(nep_iar* s, int32_t k0, int32_t count, int32_t refin
         return nep_iar_steps(s, k0, count, refine_steps, stream);
     }
     for (int32_t k = k0; k < k0 + count; ++k) {
+        if (!s->ev_mask.empty() && !s->ev_mask[k]) continue;
         if (!s->ev[k]) HIPCHK(hipEventCreateWithFlags(&s->ev[k], hipEventDisableTiming | hipEventBlockingSync));
         HIPCHK(hipEventRecord(s->ev[k], st));
+        ++s->n_ev;
     }
     if (captured) *captured = 1;
     return NEP_OK;
@@ -239,6 +263,16 @@ int32_t nep_iar_wait(nep_iar* s, int32_t k) {
         struct timespec ts = {0, 20000};
         nanosleep(&ts, nullptr);
     }
+}
+
+// *ready = 1 when column k of H has reached the pinned buffer, 0 while it has not: nep_iar_wait without the wait
+int32_t nep_iar_ready(nep_iar* s, int32_t k, int32_t* ready) {
+    ARGCHK(s && ready && k >= 1 && k <= s->m && s->ev[k]);
+    const hipError_t e = hipEventQuery(s->ev[k]);
+    if (e == hipErrorNotReady) (void)hipGetLastError();
+    else if (e != hipSuccess) HIPCHK(e);
+    *ready = e == hipSuccess ? 1 : 0;
+    return NEP_OK;
 }
 
 // orders `stream` behind step k without involving the host

@@ -37,11 +37,15 @@ int32_t nep_iar_create(nep_spmf* spmf, nep_lu* lu, int64_t n, int32_t m, nep_cdo
                        int64_t ldc, const int64_t* d_active, nep_cdouble* dwork3n, const double* h_cabs, const nep_cdouble* h_cf,
                        int32_t mt, nep_cdouble* dH, nep_cdouble* h_pinnedH, int32_t orth_method, nep_iar** out);
 int32_t nep_iar_steps_graph(nep_iar* s, int32_t k0, int32_t count, int32_t refine_steps, nep_stream stream, int32_t* captured);
+int32_t nep_iar_events_recorded(const nep_iar* s, int32_t* out);      // internal (csrc/driver.hip): feeds nep_iar_run_stats
 }
 
 namespace {
 
 constexpr double EPS = 2.220446049250313e-16;
+
+// nep_iar_run_stats: what the calling thread's last run launched (decompositions, checks, step events, rows reviewed)
+thread_local int32_t g_run_stats[4] = {0, 0, 0, 0};
 
 __global__ void k_iar_active(int64_t* act, int64_t n, int m1) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -261,17 +265,36 @@ struct Run {
 
     // rows 1..kk of the recorded H block: breakdown / DGKS flags and the refinement record (the H entries themselves stay on the
     // device: the eigen-decompositions read them there)
+    //
+    // Two readers, two paces.  check_flags(kk) changes nothing the run plans with, and runs wherever rows 1..kk are known to have
+    // arrived: in front of the check of step kk, and with every review.  fill_H(kk) also replays the refinement rule, and what that
+    // learns (Refine::recorded / hint) decides how many sweeps the LATER chunks are enqueued with: it is called from the loop
+    // only, for the row LAG steps behind the chunk being enqueued, so that the plan of every step is a function of the rows of
+    // fixed earlier steps and not of when a decomposition happened to finish -- a run with checks at every step and a run with
+    // the one check of step m take the same sweeps, in a first call as in a settled one.
     int fail_kind = 0, fail_at = 0;          // test hook NEP_IAR_RUN_FAIL_AT=kind:step (1 refinement record, 2 DGKS flag, 3 eig status)
-    int fill_H(int kk) {
-        for (int j = 1; j <= kk; ++j) {
-            if (filled[j]) continue;
-            if (fail_at == j && (fail_kind == 1 || fail_kind == 2)) {
+    int flagged = 0, reviewed = 0;           // rows 1..flagged have passed check_flags, rows 1..reviewed fill_H
+    int check_flags(int kk) {
+        for (int j = flagged + 1; j <= kk; ++j) {
+            if (fail_at == j && fail_kind == 2) {
                 retry = fail_kind; nep_set_error("nep_iar_run: injected miss of kind %d at step %d", fail_kind, j); return NEP_ERR_RETRY;
             }
             const cplx* row = a.Hpin + (int64_t)(j - 1) * (m + 4);
             const int flags = (int)row[j + 1].y;
             if (flags & 2) { nep_set_error("orthogonalisation breakdown in step %d: ||w|| = %g", j, row[j].x); return NEP_ERR_BREAKDOWN; }
             if ((flags & 1) && o.orth_method == 0) { retry = 2; nep_set_error("nep_iar_run: step %d wanted another DGKS pass", j); return NEP_ERR_RETRY; }
+            flagged = j;
+        }
+        return NEP_OK;
+    }
+    int fill_H(int kk) {
+        const int rf = check_flags(kk); if (rf) return rf;
+        for (int j = 1; j <= kk; ++j) {
+            if (filled[j]) continue;
+            if (fail_at == j && fail_kind == 1) {
+                retry = fail_kind; nep_set_error("nep_iar_run: injected miss of kind %d at step %d", fail_kind, j); return NEP_ERR_RETRY;
+            }
+            const cplx* row = a.Hpin + (int64_t)(j - 1) * (m + 4);
             if (ref.umf > 0) {
                 const int plan = plans[j];
                 const bool final_rec = !((plan & 0x100) && (j % 8) != 0);
@@ -280,12 +303,13 @@ struct Run {
                     return NEP_ERR_RETRY;
                 }
             }
-            filled[j] = 1;
+            filled[j] = 1; ++g_run_stats[3];
         }
+        reviewed = std::max(reviewed, kk);
         return NEP_OK;
     }
     ~Run() {
-        if (step) (void)nep_iar_destroy(step);
+        if (step) { (void)nep_iar_events_recorded(step, &g_run_stats[2]); (void)nep_iar_destroy(step); }
         if (V && own_V) nep_pool_free_on(V, st, true);
         if (s_QT) nep_pool_free_on(s_QT, rs.check, true);
         for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
@@ -312,6 +336,7 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
                     const nep_cdouble* h_Ctab, int32_t mt, const double* h_cabs, const nep_cdouble* h_cf, const double* h_fro,
                     nep_fv_eval fv, void* ctx, nep_cdouble* h_lam, nep_cdouble* dQ, nep_cdouble* h_Q, double* h_err,
                     nep_cdouble* dV_basis, nep_iar_result* res, nep_stream stream) {
+    for (int i = 0; i < 4; ++i) g_run_stats[i] = 0;          // (before any return: the stats are those of THIS call)
     ARGCHK(spmf && lu && opts && h_v0 && h_Ctab && fv && h_lam && res);
     ARGCHK(n > 0 && mt >= 1 && opts->maxit >= 1 && opts->check_error_every >= 1);
     ARGCHK(opts->orth_method == 0 || opts->orth_method == 1);
@@ -327,9 +352,16 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
     const int LASTB = std::max(1, nep_env_int("NEP_IAR_EIG_LAST", 8));
     const double T100 = nep_env_double("NEP_IAR_EIG_MS100", 3.3);
     const double TSTEP = 0.35;          // ms per Arnoldi step (gun, k ~ 100)
-    const int cee = opts->check_error_every;
     const double neigs = opts->neigs;
     const bool unthrottled = isinf(neigs) && neigs > 0;
+    // Which steps are checked.  With neigs = INFINITY the stop test never fires, and what the call returns comes from the check
+    // of step m alone (method_iar.jl:133-160: the errors of the earlier steps feed the logger and the stop test, nothing else):
+    // without a history buffer the checks of the steps k < m have no reader and are not made.
+    const bool nohist = unthrottled && !h_err;
+    const int cee = nohist ? m : opts->check_error_every;
+    auto due_at = [&](int kk) { return kk % cee == 0 || kk == m; };
+    const int CHUNK = unthrottled ? 8 : 4;          // steps per nep_iar_steps call
+    const int LAG = 3 * CHUNK;                      // rows are reviewed this many steps behind the chunk that is being enqueued
 
     Run R; R.spmf = spmf; R.lu = lu; R.n = n; R.o = *opts; R.fv = fv; R.ctx = ctx; R.h_fro = h_fro; R.st = as_stream(stream);
     R.m = m; R.mt = mt; R.ldv = n * (int64_t)(m + 1); R.h_err = h_err;
@@ -375,12 +407,18 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
                         R.ref.umf > 0 ? h_cabs : nullptr, R.ref.umf > 0 ? h_cf : nullptr, mt, (nep_cdouble*)a.Hdev,
                         (nep_cdouble*)a.Hpin, opts->orth_method, &R.step);
     if (rc) return rc;
+    if (nohist) {
+        // events only where something waits: the row review at the chunk ends, the one decomposition behind step m
+        std::vector<uint8_t> mask(m + 1, 0);
+        for (int kk = 1; kk <= m; ++kk) mask[kk] = (kk % CHUNK == 0 || kk == m) ? 1 : 0;
+        rc = nep_iar_event_mask(R.step, mask.data()); if (rc) return rc;
+    }
 
     // ---- batch plan of the decompositions (see checker_dev of the Python host, iar.py, for the measurements behind it)
     std::vector<char> plan_end(m + 2, 0);
     if (unthrottled) {
         std::vector<int> allk;
-        for (int kk = 1; kk <= m; ++kk) if (kk % cee == 0 || kk == m) allk.push_back(kk);
+        for (int kk = 1; kk <= m; ++kk) if (due_at(kk)) allk.push_back(kk);
         int e_ = (int)allk.size(); int size = std::min(LASTB, e_);
         while (e_ > 0) {
             plan_end[allk[e_ - 1]] = 1; e_ -= size;
@@ -395,7 +433,6 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
     double t_fv = 0;
     std::deque<int> pendA; std::deque<Batch> stA; std::deque<Check> stC;
     int slots = unthrottled ? m + 1 : std::max(BMAX, 4);
-    const int CHUNK = unthrottled ? 8 : 4;          // steps per nep_iar_steps call
     const int P = std::min(256, std::max(1, 3072 / mt));        // panel width of nep_resid_batch_dev's output layout
     int k = 1; bool done = false; int status = NEP_OK;
     const bool use_graph = nep_env_flag("NEP_IAR_GRAPH");
@@ -420,6 +457,7 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
         r = nep_hess_eigvals_batch_dev(nb, k0, kstep, (const nep_cdouble*)a.Hdev, m + 4, (nep_cdouble*)wrow, (int64_t)kstep * (m + 2),
                                        a.eigwork, a.wsz, (nep_cdouble*)mrow, (int64_t)kstep * (m + 2), (nep_stream)est);
         if (r) return r;
+        g_run_stats[0] += nb;
         b.evW = R.event(); if (!b.evW) return NEP_ERR_HIP;
         HIPCHK(hipEventRecord(b.evW, est));
         void* pz = nullptr;
@@ -436,7 +474,7 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
     // (B) of one step: Ritz values, f_t(lambda), Ritz block, residual batch -- all on the check stream
     auto launch_check = [&](const Batch& b, int bi, bool first_of_batch) -> int {
         const int kc = b.kcs[bi];
-        int r = R.fill_H(kc); if (r) return r;
+        int r = R.check_flags(kc); if (r) return r;
         const cplx* w = a.wpin + (int64_t)(kc - 1) * (m + 2);
         if (w[kc].x != 0.0 || (R.fail_kind == 3 && R.fail_at == kc)) { R.retry = 3; nep_set_error("nep_iar_run: the QR iteration of step %d gave up", kc); return NEP_ERR_RETRY; }
         Check c; c.kc = kc; c.lam.resize(2 * (size_t)kc); c.F.resize(2 * (size_t)mt * kc);
@@ -453,6 +491,7 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
             nep_set_error("nep_iar_run: the f_t(lambda) callback failed in step %d", kc); return NEP_ERR_ARG;
         }
         if (first_of_batch) HIPCHK(hipStreamWaitEvent(cst, b.evZ, 0));
+        ++g_run_stats[1];
         void* pq = nullptr;
         r = nep_pool_alloc(&pq, (size_t)n * kc * 16); if (r) return r;
         c.QT = (cplx*)pq;
@@ -527,17 +566,26 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
     hipEvent_t te0 = nullptr, te1 = nullptr; bool te1_rec = false;
     if (trace) { (void)hipEventCreate(&te0); (void)hipEventCreate(&te1); (void)hipEventRecord(te0, st); }
     const double t_loop = now();
-    double tt_steps = 0, tt_A = 0, tt_B = 0, tt_C = 0, tt_sleep = 0, t_enq_done = 0; double tq = 0;
+    double tt_steps = 0, tt_A = 0, tt_B = 0, tt_C = 0, tt_sleep = 0, t_enq_done = 0, t_m_done = 0; double tq = 0;
     while (status == NEP_OK) {
         bool progressed = false;
         tq = now();
         // recurrence: as many steps as there are free check slots (at most CHUNK) in one go
         if (!done) {
             if (k <= m && !finished()) {
+                // the rows this chunk's plan may depend on: those of the steps up to LAG behind the CHUNK-aligned block it lies
+                // in.  Not there yet (the host is LAG steps ahead of the device): nothing is enqueued in this turn.
+                const int g = (k - 1) / CHUNK * CHUNK - LAG;
+                bool gate_open = true;
+                if (g >= 1 && !R.filled[g]) {
+                    int32_t ready = 0;
+                    status = nep_iar_ready(R.step, g, &ready); if (status) break;
+                    if (ready) { status = R.fill_H(g); if (status) break; }
+                    else gate_open = false;
+                }
                 int nb = 0;
-                while (nb < CHUNK && k + nb <= m) {
-                    const bool due = ((k + nb) % cee == 0) || (k + nb == m);
-                    if (due) { if (slots <= 0) break; --slots; }
+                while (gate_open && nb < CHUNK && k + nb <= m && !(nb > 0 && (k + nb - 1) % CHUNK == 0)) {
+                    if (due_at(k + nb)) { if (slots <= 0) break; --slots; }
                     ++nb;
                 }
                 if (nb > 0) {
@@ -549,12 +597,25 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
                     if (status) break;
                     for (int kk = k; kk < k + nb; ++kk) {
                         R.plans[kk] = plan;
-                        if (kk % cee == 0 || kk == m) pendA.push_back(kk);
+                        if (due_at(kk)) pendA.push_back(kk);
                     }
                     k += nb; progressed = true;
                 }
             } else done = true;
             if (k > m) { if (!done && trace) { t_enq_done = now() - t_loop; if (te1 && !te1_rec) { (void)hipEventRecord(te1, st); te1_rec = true; } } done = true; }
+        }
+        // every step is enqueued: the rows not yet reviewed, block by block as they arrive (a miss is reported when its row is
+        // there, not when the last check is)
+        if (k > m && !finished()) {
+            while (R.reviewed < m) {
+                const int g = std::min((R.reviewed / CHUNK + 1) * CHUNK, m);
+                int32_t ready = 0;
+                status = nep_iar_ready(R.step, g, &ready); if (status || !ready) break;
+                status = R.fill_H(g); if (status) break;
+                progressed = true;
+                if (g == m && trace) t_m_done = now();
+            }
+            if (status) break;
         }
         if (trace) { const double t = now(); tt_steps += t - tq; tq = t; }
         // (A)
@@ -610,6 +671,8 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
     }
     if (te0) (void)hipEventDestroy(te0);
     if (te1) (void)hipEventDestroy(te1);
+    // nothing is returned from rows that were not reviewed (the check of step k_checked has run, so rows 1..k_checked have arrived)
+    if (status == NEP_OK && R.k_checked > 0) status = R.fill_H(R.k_checked);
     // whatever is still queued (a failure, or speculative work beyond convergence) must not outlive the blocks it uses
     while (!stA.empty()) { drop_batch(stA.front()); stA.pop_front(); }
     while (!stC.empty()) { drop_check(stC.front()); stC.pop_front(); }
@@ -641,7 +704,17 @@ int32_t nep_iar_run(nep_spmf* spmf, nep_lu* lu, int64_t n, const nep_iar_opts* o
         if (tmp) nep_pool_free(tmp);
         if (rc) { if (rc == NEP_ERR_HIP) nep_set_error("nep_iar_run: returning the eigenvector block failed"); return rc; }
     }
+    if (trace && t_m_done > 0)
+        fprintf(stderr, "nep_iar_run: %.2f ms from the arrival of step %d's row to the return (%d decompositions, %d checks)\n",
+                now() - t_m_done, m, g_run_stats[0], g_run_stats[1]);
     if (noconv) { nep_set_error("Number of iterations exceeded. maxit=%d.", m); return NEP_ERR_NOCONV; }
+    return NEP_OK;
+}
+
+// what the last nep_iar_run of the calling thread did (failed runs included, up to the failure)
+int32_t nep_iar_run_stats(int32_t out[4]) {
+    ARGCHK(out != nullptr);
+    for (int i = 0; i < 4; ++i) out[i] = g_run_stats[i];
     return NEP_OK;
 }
 

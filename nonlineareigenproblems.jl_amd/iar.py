@@ -201,7 +201,16 @@ def _route(f):
     return "step+deveig" if dev_eig else "step+hosteig"
 
 
-def _iar_native_run(nep, M0inv, orthmethod, m, tol, neigs, errkind, sigma, gamma, v, check_error_every, errhist, return_device):
+def _native_run_keeps_history(errhist, neigs, logger):
+    """whether nep_iar_run gets an error-history buffer (h_err).  Without one, and with neigs = Inf, the run checks step m only
+    (include/nepmi355.h): the errors of the steps before feed the history, the logger and the stop test, and nothing else
+    (method_iar.jl:133-160).  So the buffer is left out exactly when nobody reads it: no errhist, no logger, and a stop test
+    that cannot fire."""
+    return errhist is not None or bool(logger) or not (np.isinf(neigs) and neigs > 0)
+
+
+def _iar_native_run(nep, M0inv, orthmethod, m, tol, neigs, errkind, sigma, gamma, v, check_error_every, errhist, return_device,
+                    logger=0):
     """the whole run as ONE foreign call (csrc/iar_run.hip nep_iar_run) -- what the Julia binding's `iar(nep::DeviceSPMF; ...)`
     method calls too (julia/NEPMI355X.jl); this host only marshals the inputs (derivative table, start vector, the f_t(lambda)
     callback) and shapes the outputs.  method_iar.jl:46-182."""
@@ -235,13 +244,14 @@ def _iar_native_run(nep, M0inv, orthmethod, m, tol, neigs, errkind, sigma, gamma
     Qd = torch.empty((m, n), dtype=CDT, device="cuda") if return_device else None
     Qh = None if return_device else torch.empty((m, n), dtype=CDT, pin_memory=True)
     lam = np.zeros(m, dtype=np.complex128)
-    err = np.full((m, m), np.nan, order="F")
+    err = np.full((m, m), np.nan, order="F") if _native_run_keeps_history(errhist, neigs, logger) else None
     # (M0inv.refine puts the refinement count the run starts with into o.refine_hint and takes what the run learnt from res)
     st = M0inv.refine.native_run(o, res, lambda: lib.nep_iar_run(
         nep.dev.h, M0inv.lu.h, n, _C.addressof(o), hptr(v0), hptr(Ctab), mt,
         hptr(rc_[0]) if rc_ else None, hptr(rc_[1]) if rc_ else None, hptr(errkind[1]) if errkind[1] is not None else None,
         _C.cast(cb, c_vp), None, hptr(lam), c_vp(Qd.data_ptr()) if Qd is not None else None,
-        c_vp(Qh.data_ptr()) if Qh is not None else None, hptr(err), c_vp(V.data_ptr()), _C.addressof(res), stream_ptr()))
+        c_vp(Qh.data_ptr()) if Qh is not None else None, hptr(err) if err is not None else None, c_vp(V.data_ptr()),
+        _C.addressof(res), stream_ptr()))
     if st == NEP_ERR_RETRY:
         if res.retry_reason == 1:
             raise _RefinementMiss(0)
@@ -292,7 +302,7 @@ def _iar(nep, orthmethod=dense.DGKS, maxit=30, linsolvercreator=None, tol=EPS * 
         M0inv = create_linsolver(linsolvercreator, nep, sigma)
         if _device_lu(M0inv):
             out = _iar_native_run(nep, M0inv, orthmethod, m, tol, neigs, errkind, sigma, gamma, v, check_error_every, errhist,
-                                  return_device)
+                                  return_device, logger)
             if out is not None:
                 return out
     s = _State(t_entry, nep, orthmethod, m, linsolvercreator, M0inv, tol, neigs, errmeasure, sigma, gamma, v, check_error_every,
